@@ -23,6 +23,26 @@ Multi-GPU: `--gpus N` with no torchrun environment spawns N worker processes its
 HIP call); under torchrun the environment is used as is. Envs are sharded in contiguous blocks per rank with no
 data-path collective (weak scaling); decisions are summed and time is max-reduced over ranks.
 
+A plain run does only what its headline figure needs: set-up, warm-up, the timed steps, the result line. `--full`
+adds what takes runs of its own: the CPU baseline (`cpu_baseline`: the oracle restatement on this host's cores for
+`--cpu-seconds`, and the GPU-over-CPU ratios), unless `--no-cpu-baseline`.
+
+`--dump-outputs DIR` writes, after the timed steps, the arrays a caller of the timed path receives (the observation
+arena's tensors, the per-env accumulators and the job arrival / completion times) as DIR/<name>.npy (float32 /
+float64; the per-env scalars for every env, the larger arrays for a fixed seeded sample of envs, `env_index`). Every
+value written is finite: the +inf the engine reports as the completion time of a job still running is written as -1,
+with the job's state in `job_state`. The
+inputs (dataset, seeds, pre-roll) are identical from run to run. The shared-budget launches hand decisions to whichever
+env is ready, so how many decisions each env has taken when the timed launch ends depends on timing; each env's own
+trajectory does not (its actions are a function of the seed, the env and its decision index). So that two runs, or two
+builds, can be compared array for array, the dump first brings the timed path's final state to a fixed point of every
+trajectory (untimed): a closing launch completes the steps the timed launch preempted, then each env takes the decisions
+it has left up to the per-env cap of the launches, 8 x (warmup + steps) after the pre-roll (ssim_rollout_steps). What
+is written is thus the timed path's own state continued, not a second run; a wrong decision or event anywhere in the
+warm-up or timed launches changes it. Lockstep and step-mode runs are dumped as they end. The persistent Decima
+rollout has no per-env step count to finish with: its dump is the state as the timed launch left it, and differs from
+run to run (`outputs.comparable` in the line says which).
+
 Output: one JSON line on rank 0.
 """
 
@@ -276,6 +296,66 @@ def pmc_traffic(kernel: str, mode: str, envs: int, steps_per_launch: int, decisi
     return best[1]["hbm_bytes_per_decision"] * decisions_per_launch, os.path.relpath(best[0], REPO), best[1]
 
 
+# ------------------------------------------------------------------------------------------------ output dump
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SAMPLE_ENVS = 256
+
+
+def _save_arrays(dirpath: str, arrays: dict) -> dict:
+    """DIR/<name>.npy per array: float32 stays, everything else becomes float64 (the engine's integers fit)."""
+    import numpy as np
+
+    os.makedirs(dirpath, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32 if a.dtype == np.float32 else np.float64)
+        if not np.isfinite(a).all():
+            raise SystemExit(f"--dump-outputs: {name} holds a non-finite value")
+        total += a.nbytes
+        np.save(os.path.join(dirpath, name + ".npy"), a)
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes written, over the {DUMP_MAX_BYTES}-byte limit")
+    return {"dir": dirpath, "arrays": sorted(arrays), "bytes": total}
+
+
+def dump_outputs(dirpath: str, eng, seed: int) -> dict:
+    """The engine's current outputs as DIR/<name>.npy: counts, reward, wall_time, acc of every env; the observation
+    tensors and job times of a fixed seeded sample of envs (`env_index`). Entries past an env's node / edge / job
+    count are not part of its observation (they hold whatever an earlier observation left there) and are written as
+    zeros."""
+    import numpy as np
+
+    from spark_sched_sim import _abi
+
+    v = eng.host_views()
+    B = int(v["counts"].shape[0])
+    idx = np.sort(np.random.default_rng([seed, 64]).choice(B, min(B, DUMP_SAMPLE_ENVS), replace=False))
+    per_env = sum(int(np.prod(v[k].shape[1:])) * (4 if v[k].dtype == np.float32 else 8)
+                  for k in ("nodes", "edge_links", "dag_ptr", "exec_supplies", "frontier", "sched_rank"))
+    idx = idx[: max(1, min(len(idx), (DUMP_MAX_BYTES // 2) // max(per_env, 1)))]
+    c = np.asarray(v["counts"])[idx]
+    n, ne, nj = c[:, _abi.OC_NUM_NODES], c[:, _abi.OC_NUM_EDGES], c[:, _abi.OC_NUM_JOBS]
+
+    def valid(name, count, extra=0):
+        a = np.array(v[name][idx])
+        keep = np.arange(a.shape[1])[None, :] < (count + extra)[:, None]
+        return np.where(keep.reshape(keep.shape + (1,) * (a.ndim - 2)), a, 0)
+
+    out = {"counts": np.array(v["counts"]), "reward": np.array(v["reward"]), "wall_time": np.array(v["wall_time"]),
+           "acc": np.array(v["acc"]), "env_index": idx,
+           "nodes": valid("nodes", n), "frontier": valid("frontier", n), "sched_rank": valid("sched_rank", n),
+           "edge_links": valid("edge_links", ne), "dag_ptr": valid("dag_ptr", nj, 1),
+           "exec_supplies": valid("exec_supplies", nj)}
+    # the engine reports the completion time of a job still running (and the times of a job slot the episode does not
+    # use) as +inf; the files hold finite numbers only, so those are written as -1 (every real time is >= 0) and
+    # `job_state` says which (ssim_job_times: 0 not arrived, 1 active, 2 completed)
+    ta, tc, st = (np.asarray(x)[idx] for x in eng.job_times_np())
+    out["job_t_arrival"] = np.where(np.isfinite(ta), ta, -1.0)
+    out["job_t_completed"] = np.where(np.isfinite(tc), tc, -1.0)
+    out["job_state"] = st
+    return _save_arrays(dirpath, out)
+
+
 # ------------------------------------------------------------------------------------------------ PPO
 def run_ppo(args, rank, world, local, dev):
     """BASELINE configs[4]: whole PPO iterations (GPU rollouts with the Decima GNN, returns, baselines, PPO
@@ -339,7 +419,14 @@ def run_ppo(args, rank, world, local, dev):
             "per_rank": [{"rank": int(r), "elapsed_s": e, "decisions": int(d)} for r, e, d in per_rank],
             "phase_seconds_rank0": phases, "last_learning_stats": learn,
             "roofline": None, "cpu_baseline": None}
-        if not args.no_cpu_baseline and world == 1:
+        if args.dump_outputs:  # the last iteration's learning statistics (the rollouts share a budget: not comparable)
+            import numpy as np
+
+            line["outputs"] = _save_arrays(args.dump_outputs, {
+                "learn_" + k: np.asarray(x, dtype=np.float64) for k, x in sorted((learn or {}).items())
+                if isinstance(x, (int, float))})
+            line["outputs"]["comparable"] = False
+        if args.full and not args.no_cpu_baseline and world == 1:
             # the reference iteration's rollout phase: num_sequences x num_rollouts = 16 rollout processes
             # (trainer.py:264-296) running the Decima GNN on the CPU; an upper bound on its decisions/s (the
             # learner's time is excluded)
@@ -364,7 +451,13 @@ def main():
                          "0 = none)")
     ap.add_argument("--cpu-seconds", type=float, default=60.0)
     ap.add_argument("--cpu-procs", type=int, default=0, help="0 = every usable CPU of this job")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the CPU baseline (--cpu-seconds on every usable "
+                         "CPU) and the GPU-over-CPU ratios; a plain run only sets up, warms up, times and reports")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the arrays the timed path hands its caller as DIR/<name>.npy "
+                         "(see the module docstring)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--dataset-seed", type=int, default=0,
                     help="synthetic TPC-H-format dataset generator seed (0: stage cap 900, the bench kernel with every "
@@ -470,6 +563,10 @@ def main():
         pre_steps = np.random.default_rng([args.seed, rank, 7]).integers(0, preroll, B).astype(np.int32)
         eng.rollout_steps(kind, 4321, pre_steps, int(pre_steps.max()) + 1, flags=_abi.SSIM_ROLLOUT_WARMUP,
                           time_limits=limits)
+
+    dec_pre = None
+    if args.dump_outputs and mode == "rollout" and not args.lockstep:  # per-env decisions before the budget launches
+        dec_pre = np.array(eng.to_numpy(eng.views["acc"]), dtype=np.int64)[:, _abi.ACC_DECISIONS].copy()
 
     if mode == "decima":
         from spark_sched_sim.schedulers.decima import DecimaScheduler, build_batch
@@ -651,11 +748,30 @@ def main():
             "roofline": roofline,
             "cpu_baseline": None,
         }
+        if args.dump_outputs:  # rank 0's shard
+            if dec_pre is not None:
+                # bring every env to the same point of its own trajectory whatever share of the budget it got: complete
+                # the preempted steps, then the decisions left up to the launches' per-env cap (module docstring)
+                eng.rollout(kind, 1234, 0, flags=flags, time_limits=limits)
+                taken = np.array(eng.to_numpy(eng.views["acc"]), dtype=np.int64)[:, _abi.ACC_DECISIONS] - dec_pre
+                left = 8 * (W + K) - taken
+                if left.min() < 0:
+                    raise SystemExit(f"--dump-outputs: an env took {int(taken.max())} decisions, cap {8 * (W + K)}")
+                if left.max() > 0:
+                    eng.rollout_steps(kind, 1234, left.astype(np.int32), int(left.max()), flags=flags,
+                                      time_limits=limits)
+                eng.rollout(kind, 1234, 0, flags=flags, time_limits=limits)
+                sync()
+            line["outputs"] = dump_outputs(args.dump_outputs, eng, args.seed)
+            line["outputs"]["comparable"] = not persistent
+            line["outputs"]["state"] = ("every env continued to 8 x (warmup + steps) decisions after the pre-roll"
+                                        if dec_pre is not None else "as the timed steps left it")
         if mode == "decima":
             line["policy_overflow_envs"] = overflow
         if host:
             line["engine"] = "hostsim (TEST-ONLY CPU build; not a measurement)"
-        if not args.no_cpu_baseline and world == 1 and not host and args.workload in ("tpch", "large", "decima"):
+        if (args.full and not args.no_cpu_baseline and world == 1 and not host
+                and args.workload in ("tpch", "large", "decima")):
             procs = args.cpu_procs or usable_cpus()
             line["cpu_baseline"] = cpu_baseline(args.workload, args.cpu_seconds, procs, ds_seed=args.dataset_seed)
             add_ratios(line["cpu_baseline"], value)

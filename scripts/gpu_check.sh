@@ -31,13 +31,14 @@ for s in "$@"; do
     bench_large_nocpu) step bench_large_nocpu 300 python bench.py --workload large --steps 100 --warmup 20 --no-cpu-baseline ;;
     bench_decima_nocpu) step bench_decima_nocpu 300 python bench.py --workload decima --steps 40 --warmup 5 --no-cpu-baseline ;;
     bench_driver) step bench_driver 300 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline ;;
-    bench)   step bench 400 python bench.py ;;
+    bench_driver_cpu) step bench_driver_cpu 400 python bench.py --full --gpus 1 --steps 20 --warmup 5 ;;
+    bench)   step bench 400 python bench.py --full ;;
     bench_nocpu) step bench_nocpu 300 python bench.py --no-cpu-baseline ;;
     bench_step) step bench_step 300 python bench.py --no-cpu-baseline --mode step ;;
-    bench_decima) step bench_decima 400 python bench.py --workload decima --steps 40 --warmup 5 ;;
-    bench_ppo) step bench_ppo 900 python bench.py --workload ppo --steps 2 --warmup 1 ;;
+    bench_decima) step bench_decima 400 python bench.py --full --workload decima --steps 40 --warmup 5 ;;
+    bench_ppo) step bench_ppo 900 python bench.py --full --workload ppo --steps 2 --warmup 1 ;;
     prof_decima) step prof_decima 600 python scripts/profile_decima.py ;;
-    bench_large) step bench_large 400 python bench.py --workload large --steps 100 --warmup 20 ;;
+    bench_large) step bench_large 400 python bench.py --full --workload large --steps 100 --warmup 20 ;;
     bench_cap850) step bench_cap850 300 python bench.py --no-cpu-baseline --dataset-seed 1 ;;
     learner) step learner 600 python scripts/profile_learner.py ;;
     prof)    step prof 400 rocprofv3 --kernel-trace --stats -d "$PWD/$OUT/prof" -o run --output-format csv -- python3 bench.py --no-cpu-baseline ;;

@@ -11,7 +11,7 @@ if want tests; then bash scripts/gpu_check.sh smoke pytest || exit $?; fi
 if want bench; then
   bash scripts/gpu_check.sh bench || exit $?
   bash scripts/gpu_check.sh bench_large bench_decima bench_ppo || exit $?
-  timeout -k 10 400 python bench.py --gpus 1 --steps 20 --warmup 5 > gpurun_out/bench_driver_cpu.log 2>&1 || exit $?
+  bash scripts/gpu_check.sh bench_driver_cpu || exit $?
 fi
 if want prof; then
   bash scripts/gpu_check.sh prof prof_driver || exit $?
