@@ -902,7 +902,9 @@ __device__ __forceinline__ bool decima_policy_env(const Params* __restrict__ P, 
   lapf(7);  // (fine: exec prologue)
   float emx = -__builtin_inff(), ebest = -__builtin_inff(), es_k = 0.0f;
   int epick = -1;
-  float* escore = agg;  // [N] (agg is free after message passing)
+  // [N] (agg is free after message passing; its node_cap x 16 floats hold N scores because every caller keeps
+  // node_cap >= ceil(N / 16): ssim_decima_policy's clamp, sparksched.hip decima_lds_plan, ssim_decima_rollout's check)
+  float* escore = agg;
   if constexpr (kHelp) {  // the tiles over the workgroup's waves (dp_exec_tiles), then the same reduction
     int c = 0;
     if (spec) {  // already scored: the chosen DAG's slot

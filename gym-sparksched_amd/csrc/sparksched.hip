@@ -615,6 +615,11 @@ static DecimaLdsPlan decima_lds_plan(const Params& P, const DecimaRolloutSet& ks
   while (cap < L.stage_cap && decima_policy_lds_bytes(cap + 1, kDpLdsDags) <= room &&
          decima_scratch_bytes(cap + 1) <= room)
     ++cap;
+  // The one-wave exec-score loop keeps escore[k], k < N, in the plan's agg rows (cap x 16 floats, decima_policy.h), the
+  // reason ssim_decima_policy raises its node_cap to ceil(N / 16). A smaller LDS plan cannot hold them (a stage cap
+  // below ceil(N / 16), or the little room an -DSSIM_PROFILE / SSIM_DR_EX_LDS build leaves next to many executors'
+  // scratch): every decision then takes the global plan, which ssim_decima_rollout checks the same way.
+  if (cap < (L.num_executors + kDpEmb - 1) / kDpEmb) cap = 0;
   pl.cap = cap;
   pl.off = (int32_t)off;
   if (cap > 0) {
@@ -631,6 +636,17 @@ static DecimaLdsPlan decima_lds_plan(const Params& P, const DecimaRolloutSet& ks
 extern "C" int64_t ssim_decima_rollout_lds_bytes(const ssim_handle* h) {
   if (h == nullptr) return set_err(SSIM_E_ARG, "ssim_decima_rollout_lds_bytes: null handle");
   return decima_lds_plan(h->params, pick_decima(h->params)).lds;
+}
+
+// Test hook (host only, no launch): the node cap of the LDS plan and the waves per workgroup of the unit that
+// ssim_decima_rollout runs for this handle, so a test can say which plan a recorded decision took.
+extern "C" int ssim_debug_decima_plan(const ssim_handle* h, int32_t* cap, int32_t* waves) {
+  if (h == nullptr || cap == nullptr || waves == nullptr)
+    return set_err(SSIM_E_ARG, "ssim_debug_decima_plan: null argument");
+  const DecimaRolloutSet ks = pick_decima(h->params);
+  *cap = decima_lds_plan(h->params, ks).cap;
+  *waves = ks.waves;
+  return SSIM_OK;
 }
 
 extern "C" int64_t ssim_decima_workspace_bytes(const ssim_handle* h) {
@@ -660,6 +676,10 @@ extern "C" int ssim_decima_rollout(ssim_handle* h, const float* params, int32_t 
                    kDecimaMaxDepth);
   if (L.num_executors > 64 * kDpExecChunks)
     return set_err(SSIM_E_ARG, "ssim_decima_rollout: more than %d executors", 64 * kDpExecChunks);
+  // (the global plan's agg rows, stage_cap x 16 floats, hold the N exec scores too: decima_lds_plan)
+  if (L.stage_cap < (L.num_executors + kDpEmb - 1) / kDpEmb)
+    return set_err(SSIM_E_ARG, "ssim_decima_rollout: stage cap %d below ceil(%d executors / %d): the policy plan "
+                   "cannot hold the exec scores", L.stage_cap, L.num_executors, kDpEmb);
   const DecimaWork wl = decima_work(L);
   if (workspace_bytes < wl.total)
     return set_err(SSIM_E_ARG, "ssim_decima_rollout: workspace of %lld B, needs %lld (ssim_decima_workspace_bytes)",

@@ -304,6 +304,11 @@ int64_t ssim_decima_workspace_bytes(const ssim_handle* h);
  * policy plan, within the env's share of its compute unit (ssim_layout.lds_share). Diagnostic / sizing query. */
 int64_t ssim_decima_rollout_lds_bytes(const ssim_handle* h);
 
+/* Test hook, host only (no launch): the node cap of the LDS plan of this handle's ssim_decima_rollout launch (a decision
+ * whose observation has at most `cap` nodes and 16 DAGs runs its features and policy from LDS, any other from the env's
+ * global workspace; 0: every decision takes the global plan) and the waves per workgroup of the unit that runs it. */
+int ssim_debug_decima_plan(const ssim_handle* h, int32_t* cap, int32_t* waves);
+
 /* Decima rollouts in one launch. `params`/`num_params` as ssim_decima_policy; num_tasks_scale / work_scale as
  * ssim_decima_features. Each env takes at most `max_steps` decisions. Sampling stream: (seed, env, counter + the env's
  * decision index in its episode), plus (episode << 32) with SSIM_ROLLOUT_AUTORESET. flags:

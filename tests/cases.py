@@ -484,23 +484,61 @@ def case_decima_schedule_runs(make, dataset, env_cfg, B=16, steps=30, device="cp
         assert int(np.count_nonzero(np.asarray(c)[:, _abi.OC_ERR])) == 0
 
 
-def case_decima_fused(make, dataset, env_cfg, cfg_over, B, seed0, iters=12, device="cuda:0"):
-    """ssim_decima_policy (one fused kernel) vs the PyTorch DecimaScheduler on the same device observations:
-    stage scores of every schedulable node, exec scores of the sampled DAG, and the log-probability of the
-    sampled action, within fp32 rounding; the sampled actions are valid env actions."""
+FUSED_CONFIGS = POLICY_CONFIGS + [
+    (dict(num_executors=127, job_arrival_cap=20), 2, 630, 11),
+]
+# What the checked decisions of a fused-kernel configuration must include (case_decima_fused `expect`): after the
+# 150-decision random pre-roll the N=10 / J=50 envs hold observations of more than 64 nodes (the kernel's second
+# 64-node pass) and more than 16 schedulable stages (a second stage-score tile); the N=127 envs have commit caps above
+# 64 (the exec-score loops' second 64-action pass). The N=50 / J=200 envs reach neither within the pre-roll (their 50
+# executors drain the first jobs: at most ~36 nodes, ~11 schedulable stages on the host build).
+FUSED_EXPECT = [("nodes64", "sched16"), (), ("cap64",)]
+
+
+def _same_actions(a: dict, b: dict, rows) -> bool:
+    """Action outputs of two ssim_decima_policy calls bit for bit on the given envs (lgprob by its bits)."""
     import torch
 
+    ok = all(torch.equal(a[k][rows], b[k][rows]) for k in ("stage_idx", "num_exec", "job_idx", "exec_idx"))
+    return ok and torch.equal(a["lgprob"][rows].view(torch.int32), b["lgprob"][rows].view(torch.int32))
+
+
+def _is_none_action(a: dict, rows) -> bool:
+    """(-1, 1, -1, 0, 0.0): what the kernel returns for an env it skips (env_mask 0, more nodes than node_cap)."""
+    n = int(rows.sum())  # (rows: a bool mask over the envs)
+    got = [a[k][rows].cpu().tolist() for k in ("stage_idx", "num_exec", "job_idx", "exec_idx", "lgprob")]
+    return got == [[-1] * n, [1] * n, [-1] * n, [0] * n, [0.0] * n]
+
+
+def case_decima_fused(make, dataset, env_cfg, cfg_over, B, seed0, iters=12, device="cuda:0", preroll=150, expect=()):
+    """ssim_decima_policy (one fused kernel) vs the PyTorch DecimaScheduler on the same device observations, and vs
+    the per-observation CPU restatement (oracle/decima_gnn.py) on the reference-format observation read back from the
+    device: stage scores of every schedulable node, exec scores of the sampled DAG, and the log-probability of the
+    sampled action, within fp32 rounding; the sampled actions are valid env actions. The envs start `preroll` random
+    decisions into their episodes. The PyTorch module is compared on every env and decision; the oracle on every 4th
+    env and on the envs whose observation takes a path of `expect` ("nodes64": more than 64 nodes, "sched16": more than
+    16 schedulable stages, "cap64": a sampled DAG with more than 64 exec actions), each of which must have been checked.
+    On the first decision, one call with an env_mask (cleared envs return the "none" action, the others exactly the
+    unmasked call's) and one with node_cap below the largest node count (overflow counts the envs above it, which
+    return the "none" action; the rest exactly the full-cap call's)."""
+    import torch
+
+    from oracle import decima_gnn as G
     from spark_sched_sim.schedulers.decima import DecimaScheduler, build_batch
 
     cfg = dict(env_cfg, **cfg_over)
     N = cfg["num_executors"]
     eng = make(cfg, B, dataset, 0)
     eng.reset(seeds=[seed0 + i for i in range(B)])
+    if preroll:
+        eng.rollout(_abi.SSIM_POLICY_RANDOM, seed0, preroll)
     torch.manual_seed(seed0)
     pol = DecimaScheduler(N).to(device)
     for p in pol.parameters():
         p.data.add_(0.05 * torch.randn_like(p))
+    sd = {k: v.detach().cpu().float() for k, v in pol.state_dict().items()}
     checked = 0
+    seen = {"nodes64": 0, "sched16": 0, "cap64": 0, "oracle": 0}
     for it in range(iters):
         feats = eng.decima_features()
         b = build_batch(eng.views, feats)
@@ -509,6 +547,22 @@ def case_decima_fused(make, dataset, env_cfg, cfg_over, B, seed0, iters=12, devi
             ref = pol.stage_policy_network.scores_all(b, h)
         fo = pol.schedule_fused(eng, feats, seed=7, counter=it, with_scores=True)
         assert int(fo["overflow"].item()) == 0
+        hv = eng.host_views()
+        hf = {key: x.cpu().numpy() for key, x in feats.items()}
+        nn = np.asarray(hv["counts"])[:, _abi.OC_NUM_NODES].astype(np.int64)
+        if it == 0:
+            keep = torch.tensor([e % 3 != 1 for e in range(B)], device=device)
+            fm = pol.schedule_fused(eng, feats, seed=7, counter=it, env_mask=keep)
+            assert int(fm["overflow"].item()) == 0
+            assert _is_none_action(fm, ~keep), "env_mask: a cleared env's outputs"
+            assert _same_actions(fm, fo, keep), "env_mask: the other envs' outputs changed"
+            ncap = int(np.sort(nn)[B // 2])  # the median node count: below the largest, above ceil(N / 16)
+            assert (N + 15) // 16 <= ncap < int(nn.max()), (ncap, nn)
+            over = torch.from_numpy(nn > ncap).to(device)
+            fc = pol.schedule_fused(eng, feats, seed=7, counter=it, node_cap=ncap)
+            assert int(fc["overflow"].item()) == int(over.sum().item()) > 0, (fc["overflow"], over.sum())
+            assert _is_none_action(fc, over), "node_cap: an env above the cap"
+            assert _same_actions(fc, fo, ~over), "node_cap: the envs within the cap changed"
         si, ji, ei = fo["stage_idx"].cpu(), fo["job_idx"].cpu(), fo["exec_idx"].cpu()
         ss, lg = fo["stage_scores"].cpu(), fo["lgprob"].cpu()
         node_env, mask = b.node_env.cpu(), b.stage_mask.cpu()
@@ -532,11 +586,31 @@ def case_decima_fused(make, dataset, env_cfg, cfg_over, B, seed0, iters=12, devi
                     + torch.log_softmax(es[0, :cap].cpu(), 0)[int(ei[e])])
             assert abs(float(lg[e]) - float(want)) <= 1e-4 + 1e-4 * abs(float(want)), f"env{e} lgprob"
             checked += 1
+            paths = [name for name, hit in (("nodes64", int(nn[e]) > 64), ("sched16", rows.numel() > 16),
+                                            ("cap64", cap > 64)) if hit]
+            if (e + it) % 4 == 0 or any(seen[name] < 3 for name in paths):
+                # the oracle on the reference-format observation (oracle/decima_gnn.py), the same tolerances
+                ro = decima_obs_dict(hv, hf, e, N)
+                enc = G.encode(sd, ro)
+                rs = G.stage_scores(sd, ro, enc)
+                assert torch.allclose(got, rs, rtol=1e-4, atol=1e-5), f"env{e} it{it} stage scores vs oracle"
+                assert G.job_of_stage(ro, int(si[e])) == int(ji[e]), f"env{e} it{it} job of the stage"
+                re_ = G.exec_scores(sd, ro, enc, int(ji[e]), N)
+                assert re_.numel() == cap, f"env{e} it{it} exec cap {cap} vs oracle {re_.numel()}"
+                assert torch.allclose(fo["exec_scores"][e, :cap].cpu(), re_, rtol=1e-4, atol=1e-5), \
+                    f"env{e} it{it} exec scores vs oracle"
+                want_o = float(torch.log_softmax(rs, 0)[int(si[e])] + torch.log_softmax(re_, 0)[int(ei[e])])
+                assert abs(float(lg[e]) - want_o) <= 1e-4 + 1e-4 * abs(want_o), f"env{e} it{it} lgprob vs oracle"
+                seen["oracle"] += 1
+                for name in paths:
+                    seen[name] += 1
         eng.step(fo["stage_idx"], fo["num_exec"])
         c = eng.host_views()["counts"]
         assert int(np.count_nonzero(np.asarray(c)[:, _abi.OC_ERR])) == 0
         eng.rollout(_abi.SSIM_POLICY_RANDOM, 3 + it, 4)
     assert checked > B * iters // 2
+    assert seen["oracle"] >= checked // 4 and all(seen[name] > 0 for name in expect), seen
+    return seen
 
 
 def case_async_rollouts(make, dataset, env_cfg, device="cpu", B=6, calls=3, duration=2.5e5, mean_limit=4e5):

@@ -1,0 +1,388 @@
+"""TEST INFRASTRUCTURE ONLY — audits a filled sample arena of the persistent Decima rollout (ssim_decima_rollout,
+csrc/decima_rollout.h) against the CPU oracle: the env (oracle/restatement.py), the Decima observation wrapper
+(oracle/decima.py), the per-observation fp32 GNN policy (oracle/decima_gnn.py) and a numpy restatement of the device
+sampling stream (csrc/policy.h splitmix64, csrc/decima_policy.h dp_gumbel).
+
+The replay tests show the engine is right GIVEN the rollout's actions; this module checks what the rollout computed
+to choose them: every recorded observation row, the log-probability and the Gumbel-max draw of the recorded action.
+
+  gumbel_np           the device's Gumbel noise for (seed, env, counter, item), stage or exec draw
+  host_arena          numpy copies of a DecimaSampleArena (any device)
+  sample_observation  the reference-format Decima observation of one recorded sample
+  audit               the checks, per env; raises parity.Mismatch, returns per-sample sizes and path classes
+  reference_rollout   the same walk with the reference's own winners as actions (what a correct kernel records)
+  collect_reference   a sample arena filled on the host build of the engine, actions from the oracle policy
+"""
+
+from __future__ import annotations
+
+from types import SimpleNamespace
+
+import numpy as np
+import torch
+
+import parity
+from oracle import decima_gnn as G
+from oracle.decima import decima_observation
+from oracle.restatement import SparkSchedOracle
+from spark_sched_sim import _abi
+from spark_sched_sim.engine import GraphInstance
+
+M64 = (1 << 64) - 1
+EXEC_DRAW_KEY = 0xE7037ED1A0B428DB  # decima_policy.h: the exec draw's key is the decision's key ^ this
+LGPROB_ATOL = LGPROB_RTOL = 1e-4    # cases.case_decima_fused's bar for the fused kernel's log-probability
+SCORE_ATOL, SCORE_RTOL = 1e-5, 1e-4  # cases.case_decima_fused's bar per score
+MAX_SKIP_SHARE = 0.02
+LDS_PLAN_DAGS = 16   # decima_policy.h kDpLdsDags
+HELP_WAVES, SPEC_CAND, TILE = 4, 3, 16  # decima_policy.h kDpHelpWaves, kDpSpecCand, rows per exec-score tile
+I32 = {name: i for i, name in enumerate(_abi.SAMPLE_I32)}
+
+
+# ------------------------------------------------------------------------------------------ the sampling stream
+def _splitmix64(x: int) -> int:
+    """policy.h:17 on a python int."""
+    x = (x + 0x9E3779B97F4A7C15) & M64
+    x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & M64
+    x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & M64
+    return x ^ (x >> 31)
+
+
+def _splitmix64_np(x: np.ndarray) -> np.ndarray:
+    with np.errstate(over="ignore"):
+        x = x + np.uint64(0x9E3779B97F4A7C15)
+        x = (x ^ (x >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        x = (x ^ (x >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        return x ^ (x >> np.uint64(31))
+
+
+def decision_key(seed: int, env: int, counter: int) -> int:
+    """decima_policy.h:780: key = splitmix64(seed ^ splitmix64(eid * 0x9E3779B97F4A7C15 + counter))."""
+    return _splitmix64((seed & M64) ^ _splitmix64((env * 0x9E3779B97F4A7C15 + counter) & M64))
+
+
+def gumbel_np(seed: int, env: int, counter: int, items, exec_draw: bool = False) -> np.ndarray:
+    """dp_gumbel(key, item) for every item (node index for the stage draw, exec action k for the exec draw), as float32:
+    r = splitmix64(key ^ splitmix64(item + 0x632BE59BD9B4E019)), u = ((r >> 11) + 0.5) / 2^53, -log(-log(u)) in float64,
+    rounded to float32. `counter` is the launch's counter plus the decision's index in its episode."""
+    key = decision_key(seed, env, counter) ^ (EXEC_DRAW_KEY if exec_draw else 0)
+    it = np.asarray(items, dtype=np.uint64).reshape(-1)
+    with np.errstate(over="ignore"):
+        r = _splitmix64_np(np.uint64(key) ^ _splitmix64_np(it + np.uint64(0x632BE59BD9B4E019)))
+    u = ((r >> np.uint64(11)).astype(np.float64) + 0.5) * (1.0 / 9007199254740992.0)
+    return (-np.log(-np.log(u))).astype(np.float32)
+
+
+# ------------------------------------------------------------------------------------------ arena access
+def host_arena(arena) -> SimpleNamespace:
+    """Host (numpy) copies of a DecimaSampleArena's cursor, records and node / edge / DAG rows."""
+    def np_(t):
+        return t.detach().cpu().numpy().copy() if isinstance(t, torch.Tensor) else np.array(t)
+
+    return SimpleNamespace(cursor=np_(arena.cursor), rec=np_(arena.rec), nodes=np_(arena.nodes),
+                           edges=np_(arena.edges), dags=np_(arena.dags))
+
+
+def sample_record(arena, env: int, k: int) -> dict:
+    """Sample k of env as a dict: the int32 fields (_abi.SAMPLE_I32), lgprob, wall_before, reward."""
+    words = np.ascontiguousarray(arena.rec[env, k])
+    r = {name: int(words[i]) for name, i in I32.items()}
+    r["lgprob"] = float(words.view(np.float32)[_abi.SAMPLE_LGPROB])
+    r["wall_before"] = float(words.view(np.float64)[_abi.SAMPLE_WALL])
+    r["reward"] = float(words.view(np.float64)[_abi.SAMPLE_REWARD])
+    return r
+
+
+def sample_observation(arena, env: int, k: int, num_executors: int) -> dict:
+    """The reference-format Decima observation (schedulers/decima/env_wrapper.py:98-104) of sample k of env, from
+    its arena rows, as engine.decima_obs_dict builds it from the obs arena and the feature arrays."""
+    r = sample_record(arena, env, k)
+    n, ne, nj, depth = r["num_nodes"], r["num_edges"], r["num_dags"], r["depth"]
+    rows = np.array(arena.nodes[env, r["node_off"]: r["node_off"] + n], dtype=np.float32).reshape(n, 6)
+    ed = np.asarray(arena.edges[env, r["edge_off"]: r["edge_off"] + ne]).reshape(ne, 4)
+    dg = np.asarray(arena.dags[env, r["dag_off"]: r["dag_off"] + nj]).reshape(nj, 2)
+    words = ed[:, 2].astype(np.int64).astype(np.uint32)
+    levels = np.arange(max(depth - 1, 0), dtype=np.uint32)
+    return {
+        "dag_batch": GraphInstance(np.ascontiguousarray(rows[:, :5]), np.zeros(ne, dtype=np.int64),
+                                   ed[:, :2].astype(np.int64).reshape(ne, 2)),
+        "dag_ptr": [0] + [int(x) for x in np.cumsum(dg[:, 0].astype(np.int64))],
+        "stage_mask": rows[:, 5] != 0,
+        "exec_mask": np.arange(num_executors)[None, :] < dg[:, 1].astype(np.int64)[:, None],
+        "edge_masks": ((words[None, :] >> levels[:, None]) & 1).astype(bool),
+    }
+
+
+# ------------------------------------------------------------------------------------------ path classification
+def classify(dobs: dict, job_idx: int, num_executors: int, plan_cap: int, helper: bool) -> tuple[str, str]:
+    """Which paths of the rollout a decision on this observation takes, from the observation alone.
+    plan (decima_rollout.h:193): "lds" if n <= plan_cap and nj <= 16, else "global".
+    exec_path, helper units only (decima_policy.h:803-824 and :923; "" otherwise): with at most 64 schedulable nodes,
+    the distinct DAGs of the schedulable nodes in node order; "spec" if they are at most 3 and their caps, clamped to
+    [0, N], need 1..3 tiles of 16 exec actions in all; else "many" if the chosen DAG's cap exceeds 16, else "single"."""
+    n = dobs["stage_mask"].shape[0]
+    ptr = np.asarray(dobs["dag_ptr"], dtype=np.int64)
+    nj = len(ptr) - 1
+    plan = "lds" if n <= plan_cap and nj <= LDS_PLAN_DAGS else "global"
+    if not helper:
+        return plan, ""
+    caps = np.clip(np.asarray(dobs["exec_mask"], dtype=bool).sum(axis=1), 0, num_executors)
+    sched = np.flatnonzero(dobs["stage_mask"])
+    spec = False
+    if len(sched) <= 64:
+        dags, tiles, over = [], 0, False
+        for g in np.searchsorted(ptr, sched, side="right") - 1:
+            if g in dags:
+                continue
+            if len(dags) == SPEC_CAND:
+                over = True
+                break
+            dags.append(int(g))
+            tiles += (int(caps[g]) + TILE - 1) // TILE
+        spec = not over and 0 < tiles < HELP_WAVES
+    if spec:
+        return plan, "spec"
+    return plan, "many" if int(caps[job_idx]) > TILE else "single"
+
+
+# ------------------------------------------------------------------------------------------ the walk
+def _policy(sd: dict, dobs: dict, num_executors: int, seed: int, env: int, ctr: int, stage_of=None,
+            stage_key_exec: bool = False):
+    """The oracle policy on one observation and the device stream's draws: stage scores, their Gumbel-max winner and
+    its lead over the runner-up; then, for the DAG of stage `stage_of` (default: the winner), the same for the exec
+    scores. Scores are float32 (the oracle's), noise added in float32 as the kernel adds it."""
+    enc = G.encode(sd, dobs)
+    ss = G.stage_scores(sd, dobs, enc)
+    sched = np.flatnonzero(np.asarray(dobs["stage_mask"], dtype=bool))
+    gs = ss.numpy().astype(np.float32) + gumbel_np(seed, env, ctr, sched, exec_draw=stage_key_exec)
+    s_win = int(np.argmax(gs))
+    s_lead = float(gs[s_win] - np.partition(gs, -2)[-2]) if gs.size > 1 else np.inf
+    si = s_win if stage_of is None else stage_of
+    job = G.job_of_stage(dobs, si)
+    es = G.exec_scores(sd, dobs, enc, job, num_executors)
+    ge = es.numpy().astype(np.float32) + gumbel_np(seed, env, ctr, np.arange(es.numel()), exec_draw=True)
+    e_win = int(np.argmax(ge)) if ge.size else 0
+    e_lead = float(ge[e_win] - np.partition(ge, -2)[-2]) if ge.size > 1 else np.inf
+    return SimpleNamespace(ss=ss, es=es, job=job, s_win=s_win, s_lead=s_lead, e_win=e_win, e_lead=e_lead,
+                           s_margin=2.0 * (SCORE_ATOL + SCORE_RTOL * float(ss.abs().max())),
+                           e_margin=2.0 * (SCORE_ATOL + SCORE_RTOL * float(es.abs().max())) if es.numel() else 0.0)
+
+
+def _lgprob(p, si: int, ei: int) -> float:
+    return float(torch.log_softmax(p.ss, 0)[si] + torch.log_softmax(p.es, 0)[ei])
+
+
+def _walk_env(env_cfg, dataset, env, env_seed, limit, sd, seed, counter, arena, every, plan_cap, helper, complete,
+              max_decisions, stage_key_exec=False):
+    """One env: the oracle from reset(env_seed, limit) through the recorded samples (arena given: every check of
+    `audit`), or through the reference's own winners (arena None). Returns the per-sample rows of the report."""
+    N = env_cfg["num_executors"]
+    limit = float("inf") if limit is None else float(limit)
+    o = SparkSchedOracle(env_cfg, dataset)
+    obs, _ = o.reset(seed=int(env_seed), options={"time_limit": limit})
+    ns = int(arena.cursor[env, _abi.CUR_SAMPLES]) if arena is not None else max_decisions
+    rows, over = [], False
+    off = [0, 0, 0]
+    for k in range(ns):
+        where = f"env{env} sample{k}"
+        if over:
+            if arena is None:
+                break
+            raise parity.Mismatch(f"{where}: recorded after the reference episode ended ({k} decisions)")
+        dobs = decima_observation(obs, N)
+        audited = k % every == 0
+        if arena is not None:
+            r = sample_record(arena, env, k)
+            got = sample_observation(arena, env, k, N)
+            parity.compare_decima(dobs, got, where)
+            if np.float64(r["wall_before"]).tobytes() != np.float64(o.wall_time).tobytes():
+                raise parity.Mismatch(f"{where}: wall_before {r['wall_before']!r} != {float(o.wall_time)!r}")
+            # record consistency
+            want_off = {"node_off": off[0], "edge_off": off[1], "dag_off": off[2]}
+            for name, w in want_off.items():
+                if r[name] != w:
+                    raise parity.Mismatch(f"{where}: {name} {r[name]} != running sum {w}")
+            off = [off[0] + r["num_nodes"], off[1] + r["num_edges"], off[2] + r["num_dags"]]
+            levels = int(np.asarray(dobs["edge_masks"]).shape[0])
+            if max(r["depth"] - 1, 0) != levels:
+                raise parity.Mismatch(f"{where}: depth {r['depth']} vs {levels} oracle edge-mask levels")
+            nsch = int(np.count_nonzero(dobs["stage_mask"]))
+            if not 0 <= r["stage_idx"] < nsch:
+                raise parity.Mismatch(f"{where}: stage_idx {r['stage_idx']} outside the {nsch} schedulable stages")
+            job = G.job_of_stage(dobs, r["stage_idx"])
+            if r["job_idx"] != job:
+                raise parity.Mismatch(f"{where}: job_idx {r['job_idx']} != job of stage {r['stage_idx']} ({job})")
+            cap = int(dobs["commit_caps"][job])
+            if r["num_exec"] != r["exec_idx"] + 1:
+                raise parity.Mismatch(f"{where}: num_exec {r['num_exec']} != exec_idx {r['exec_idx']} + 1")
+            if not 0 <= r["exec_idx"] < cap:
+                raise parity.Mismatch(f"{where}: exec_idx {r['exec_idx']} outside commit cap {cap} of job {job}")
+            si, ei = r["stage_idx"], r["exec_idx"]
+        skipped = False
+        if audited or arena is None:
+            p = _policy(sd, dobs, N, seed, env, (counter + k) & M64, stage_of=si if arena is not None else None,
+                        stage_key_exec=stage_key_exec)
+            s_clear, e_clear = p.s_lead > p.s_margin, p.e_lead > p.e_margin
+            skipped = not (s_clear and e_clear)
+            if arena is None:
+                si, ei, job = p.s_win, p.e_win, p.job
+                cap = int(dobs["commit_caps"][job])
+                lg = _lgprob(p, si, ei)
+            else:
+                if s_clear and p.s_win != si:
+                    raise parity.Mismatch(f"{where}: stage draw: recorded {si}, the reference's Gumbel-max winner is "
+                                          f"{p.s_win} by {p.s_lead:.3e} (margin {p.s_margin:.3e})")
+                if e_clear and p.e_win != ei:
+                    raise parity.Mismatch(f"{where}: exec draw: recorded {ei}, the reference's Gumbel-max winner is "
+                                          f"{p.e_win} by {p.e_lead:.3e} (margin {p.e_margin:.3e})")
+                want = _lgprob(p, si, ei)
+                if not abs(r["lgprob"] - want) <= LGPROB_ATOL + LGPROB_RTOL * abs(want):
+                    raise parity.Mismatch(f"{where}: lgprob {r['lgprob']!r} vs oracle {want!r} "
+                                          f"(diff {abs(r['lgprob'] - want):.3e})")
+        plan, exec_path = classify(dobs, job, N, plan_cap, helper)
+        rows.append(dict(env=env, k=k, nodes=int(dobs["stage_mask"].shape[0]), dags=len(dobs["dag_ptr"]) - 1,
+                         sched=int(np.count_nonzero(dobs["stage_mask"])), cap=cap, plan=plan, exec_path=exec_path,
+                         audited=bool(audited or arena is None), skipped=bool(skipped), stage_idx=si, exec_idx=ei,
+                         job_idx=job, lgprob=(lg if arena is None else r["lgprob"])))
+        try:
+            obs, rew, term, _, info = o.step({"stage_idx": int(si), "num_exec": int(ei) + 1})
+        except (ValueError, KeyError) as err:
+            raise parity.Mismatch(f"{where}: the oracle env refuses the recorded action ({si}, {ei + 1}): {err}")
+        if arena is not None and not parity.reward_close(r["reward"], float(rew), o.beta, len(o.jobs)):
+            raise parity.Mismatch(f"{where}: reward {r['reward']!r} != {rew!r}")
+        over = bool(term) or info["wall_time"] >= limit
+    if arena is not None and complete and not over:
+        raise parity.Mismatch(f"env{env}: {ns} samples recorded, the reference episode goes on (wall {o.wall_time!r}, "
+                              f"limit {limit!r})")
+    return rows
+
+
+def _report(rows: list[dict], what: str) -> dict:
+    rep = {key: np.array([r[key] for r in rows]) for key in rows[0]} if rows else {}
+    aud = int(rep["audited"].sum()) if rows else 0
+    skp = int((rep["audited"] & rep["skipped"]).sum()) if rows else 0
+    rep["audited_draws"], rep["skipped_draws"] = aud, skp
+    rep["skip_share"] = skp / aud if aud else 0.0
+    rep["plan_counts"] = {p: int((rep["plan"] == p).sum()) if rows else 0 for p in ("lds", "global")}
+    rep["exec_path_counts"] = {p: int((rep["exec_path"] == p).sum()) if rows else 0 for p in ("spec", "many", "single")}
+    if rep["skip_share"] > MAX_SKIP_SHARE:
+        raise parity.Mismatch(f"{what}: {skp} of {aud} audited draws inside the score margin "
+                              f"({rep['skip_share']:.1%} > {MAX_SKIP_SHARE:.0%})")
+    return rep
+
+
+def audit(arena, env_cfg: dict, dataset, seeds, limits, sd: dict, seed: int, counter: int, every: int = 1,
+          plan_cap: int = 0, helper: bool = False, complete: bool = True, envs=None) -> dict:
+    """Audits a filled sample arena (host copies: host_arena) of ONE collection (no auto-reset) that started with
+    reset(seeds[e], limits[e]) and ran with the launch parameters (seed, counter); `sd`: the policy's state_dict,
+    fp32 on the CPU. Per env, raising parity.Mismatch on the first failure:
+
+    Env and features, every sample: a SparkSchedOracle is driven through the recorded (stage_idx, num_exec); before each
+    step its Decima observation equals sample_observation under parity.compare_decima (float32 features bit for bit,
+    links, dag_ptr and the three masks equal), wall_before equals the oracle's wall time bit for bit, the reward passes
+    parity.reward_close; after the last sample the oracle's episode is over (`complete`).
+    Record consistency, every sample: num_exec == exec_idx + 1, 0 <= exec_idx < the job's commit cap, job_idx the DAG of
+    the stage, the row offsets the running sums of the earlier samples' counts, depth the oracle's edge-mask levels.
+    Policy value, every `every`-th sample: lgprob within 1e-4 + 1e-4 |want| of log_softmax(stage scores)[stage_idx] +
+    log_softmax(exec scores)[exec_idx] of oracle/decima_gnn.py.
+    Draw, the same samples: the Gumbel-max winners of the oracle's scores plus gumbel_np equal the recorded choices
+    wherever the winner leads the runner-up by more than 2 * (1e-5 + 1e-4 max|score|); decisions inside that margin
+    are skipped and counted, more than 2% skipped fails.
+
+    Returns the per-sample arrays env, k, nodes, dags, sched, cap (commit cap of the chosen job), plan, exec_path
+    (classify), audited, skipped, and audited_draws, skipped_draws, skip_share, plan_counts, exec_path_counts."""
+    B = arena.cursor.shape[0]
+    rows = []
+    for e in (range(B) if envs is None else envs):
+        rows += _walk_env(env_cfg, dataset, e, seeds[e], None if limits is None else limits[e], sd, seed, counter,
+                          arena, every, plan_cap, helper, complete, 0)
+    return _report(rows, "audit")
+
+
+def reference_rollout(env_cfg: dict, dataset, seeds, limits, sd: dict, seed: int, counter: int, plan_cap: int = 0,
+                      helper: bool = False, max_decisions: int = 10**9, stage_key_exec: bool = False) -> dict:
+    """The collection a correct kernel records, without an engine: per env the oracle from reset(seeds[e], limits[e])
+    with the reference's own Gumbel-max winners as actions, until the episode ends. The report of `audit` (every
+    decision counts as audited), plus stage_idx / exec_idx / job_idx / lgprob per sample."""
+    rows = []
+    for e in range(len(seeds)):
+        rows += _walk_env(env_cfg, dataset, e, seeds[e], None if limits is None else limits[e], sd, seed, counter,
+                          None, 1, plan_cap, helper, True, max_decisions, stage_key_exec)
+    return _report(rows, "reference rollout")
+
+
+# ------------------------------------------------------------------------------------------ a host-filled arena
+def fill_arena_like_kernel(arena, e, v, f):
+    """What csrc/decima_rollout.h DecimaPolicy.act writes for env e's current observation (host views v, host
+    features f): the node / edge / DAG rows after the env's cursor, and the record (action fields left 0)."""
+    c = v["counts"][e]
+    n, ne, nj = int(c[_abi.OC_NUM_NODES]), int(c[_abi.OC_NUM_EDGES]), int(c[_abi.OC_NUM_JOBS])
+    cur = arena.cursor[e]
+    cs, cn, ce, cg = (int(x) for x in cur[:4])
+    arena.nodes[e, cn:cn + n, :5] = torch.from_numpy(np.asarray(f["node_feats"][e, :n]))
+    arena.nodes[e, cn:cn + n, 5] = torch.from_numpy(np.asarray(v["nodes"][e, :n, 2]))
+    links = np.asarray(v["edge_links"][e, :ne], dtype=np.int64)
+    arena.edges[e, ce:ce + ne, 0] = torch.from_numpy(links[:, 0].astype(np.int32))
+    arena.edges[e, ce:ce + ne, 1] = torch.from_numpy(links[:, 1].astype(np.int32))
+    arena.edges[e, ce:ce + ne, 2] = torch.from_numpy(np.asarray(f["edge_mask"][e, :ne]).astype(np.int32))
+    ptr = np.asarray(v["dag_ptr"][e, : nj + 1], dtype=np.int64)
+    arena.dags[e, cg:cg + nj, 0] = torch.from_numpy((ptr[1:] - ptr[:-1]).astype(np.int32))
+    arena.dags[e, cg:cg + nj, 1] = torch.from_numpy(np.asarray(f["commit_cap"][e, :nj]).astype(np.int32))
+    rec = torch.zeros(16, dtype=torch.int32)
+    rec[:7] = torch.tensor([n, ne, nj, int(f["depth"][e]), cn, ce, cg], dtype=torch.int32)
+    arena.rec[e, cs] = rec
+    cur[:4] = torch.tensor([cs + 1, cn + n, ce + ne, cg + nj], dtype=torch.int32)
+
+
+def collect_reference(eng, arena, seeds, limits, sd: dict, seed: int, counter: int, stage_key_exec: bool = False):
+    """One collection on the host build of the engine (hostsim.driver.HostEngine `eng`) into the CPU DecimaSampleArena
+    `arena`, the way the kernel runs it: per env reset(seeds[e], limits[e]), then until the episode ends (terminated,
+    or wall time >= the limit) the observation rows (fill_arena_like_kernel, the arena grown when a region is full),
+    the action the oracle policy (oracle/decima_gnn.py on the engine's observation and features) draws with gumbel_np
+    on (seed, env, counter + decision index), its oracle log-probability, the wall time, and after the step the
+    reward. stage_key_exec: the stage draw keyed with the exec draw's constant (a wrong stream: the mutation test)."""
+    from spark_sched_sim.engine import decima_obs_dict
+
+    B, N = eng.num_envs, eng.layout.num_executors
+    limits = [float("inf") if x is None else float(x) for x in (limits if limits is not None else [None] * B)]
+    eng.reset(seeds=[int(s) for s in seeds], options=[{"time_limit": x} for x in limits])
+    live = [True] * B
+    k = 0
+    while any(live):
+        v = eng.host_views()
+        f = eng.decima_features_np()
+        si, ne = np.full(B, -1, dtype=np.int32), np.ones(B, dtype=np.int32)
+        for e in range(B):
+            if not live[e]:
+                continue
+            c = v["counts"][e]
+            need = [int(arena.cursor[e, 0]) + 1, int(arena.cursor[e, 1]) + int(c[_abi.OC_NUM_NODES]),
+                    int(arena.cursor[e, 2]) + int(c[_abi.OC_NUM_EDGES]),
+                    int(arena.cursor[e, 3]) + int(c[_abi.OC_NUM_JOBS])]
+            if any(n > cap for n, cap in zip(need, arena.caps)):  # the kernel's full flag and needs
+                arena.cursor[e, _abi.CUR_FULL] = 1
+                arena.cursor[e, _abi.CUR_NEED_NODES] = int(c[_abi.OC_NUM_NODES])
+                arena.cursor[e, _abi.CUR_NEED_EDGES] = int(c[_abi.OC_NUM_EDGES])
+                arena.cursor[e, _abi.CUR_NEED_DAGS] = int(c[_abi.OC_NUM_JOBS])
+                arena.grow(arena.cursor.numpy())
+            cs = int(arena.cursor[e, 0])
+            fill_arena_like_kernel(arena, e, v, f)
+            dobs = decima_obs_dict(v, f, e, N)
+            p = _policy(sd, dobs, N, seed, e, (counter + k) & M64, stage_key_exec=stage_key_exec)
+            si[e], ne[e] = p.s_win, p.e_win + 1
+            words = arena.rec[e, cs]
+            words[I32["stage_idx"]], words[I32["job_idx"]] = p.s_win, p.job
+            words[I32["exec_idx"]], words[I32["num_exec"]] = p.e_win, p.e_win + 1
+            words.view(torch.float32)[_abi.SAMPLE_LGPROB] = _lgprob(p, p.s_win, p.e_win)
+            words.view(torch.float64)[_abi.SAMPLE_WALL] = float(v["wall_time"][e])
+        eng.step(si, ne)
+        v = eng.host_views()
+        for e in range(B):
+            if not live[e]:
+                continue
+            c = v["counts"][e]
+            assert int(c[_abi.OC_ERR]) == 0, f"env{e} decision {k}: engine error bits {int(c[_abi.OC_ERR]):#x}"
+            cs = int(arena.cursor[e, 0])
+            arena.rec[e, cs - 1].view(torch.float64)[_abi.SAMPLE_REWARD] = float(v["reward"][e])
+            live[e] = not (bool(c[_abi.OC_TERMINATED]) or float(v["wall_time"][e]) >= limits[e])
+        k += 1
+    return arena

@@ -48,11 +48,13 @@ def test_decima_schedule_gpu(gpu_device, dataset, env_cfg):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("cfg_over,B,seed0,every", cases.POLICY_CONFIGS)
+@pytest.mark.parametrize("cfg_over,B,seed0,every", cases.FUSED_CONFIGS)
 def test_decima_fused_kernel_gpu(gpu_device, dataset, env_cfg, cfg_over, B, seed0, every):
     from spark_sched_sim.engine import DeviceEngine
 
     def make(cfg, B, ds, trace_cap):
         return DeviceEngine(cfg, B, ds, device=gpu_device, trace_cap=trace_cap)
 
-    cases.case_decima_fused(make, dataset, env_cfg, cfg_over, 32, seed0, device=gpu_device)
+    expect = cases.FUSED_EXPECT[[c[0] for c in cases.FUSED_CONFIGS].index(cfg_over)]
+    seen = cases.case_decima_fused(make, dataset, env_cfg, cfg_over, 32, seed0, device=gpu_device, expect=expect)
+    print(f"fused kernel {cfg_over}: decisions checked against the oracle and the paths among them: {seen}")

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+from decima_audit import fill_arena_like_kernel as _fill_arena_like_kernel
 from oracle import trainer_utils as TU
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -446,30 +447,6 @@ def _batch_equal(want, got, what):
             assert a.dtype == b.dtype and a.shape == b.shape and torch.equal(a.cpu(), b.cpu()), f"{what}: {name}"
         else:
             assert a == b, f"{what}: {name}"
-
-
-def _fill_arena_like_kernel(arena, e, v, f):
-    """What csrc/decima_rollout.h DecimaPolicy.act writes for env e's current observation (host views v, host
-    features f): the node / edge / DAG rows after the env's cursor, and the record (action fields left 0)."""
-    from spark_sched_sim import _abi
-
-    c = v["counts"][e]
-    n, ne, nj = int(c[_abi.OC_NUM_NODES]), int(c[_abi.OC_NUM_EDGES]), int(c[_abi.OC_NUM_JOBS])
-    cur = arena.cursor[e]
-    cs, cn, ce, cg = (int(x) for x in cur[:4])
-    arena.nodes[e, cn:cn + n, :5] = torch.from_numpy(np.asarray(f["node_feats"][e, :n]))
-    arena.nodes[e, cn:cn + n, 5] = torch.from_numpy(np.asarray(v["nodes"][e, :n, 2]))
-    links = np.asarray(v["edge_links"][e, :ne], dtype=np.int64)
-    arena.edges[e, ce:ce + ne, 0] = torch.from_numpy(links[:, 0].astype(np.int32))
-    arena.edges[e, ce:ce + ne, 1] = torch.from_numpy(links[:, 1].astype(np.int32))
-    arena.edges[e, ce:ce + ne, 2] = torch.from_numpy(np.asarray(f["edge_mask"][e, :ne]).astype(np.int32))
-    ptr = np.asarray(v["dag_ptr"][e, : nj + 1], dtype=np.int64)
-    arena.dags[e, cg:cg + nj, 0] = torch.from_numpy((ptr[1:] - ptr[:-1]).astype(np.int32))
-    arena.dags[e, cg:cg + nj, 1] = torch.from_numpy(np.asarray(f["commit_cap"][e, :nj]).astype(np.int32))
-    rec = torch.zeros(16, dtype=torch.int32)
-    rec[:7] = torch.tensor([n, ne, nj, int(f["depth"][e]), cn, ce, cg], dtype=torch.int32)
-    arena.rec[e, cs] = rec
-    cur[:4] = torch.tensor([cs + 1, cn + n, ce + ne, cg + nj], dtype=torch.int32)
 
 
 def test_arena_buffer_matches_per_step_batches(dataset):
