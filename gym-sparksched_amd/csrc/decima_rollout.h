@@ -17,6 +17,8 @@
 // episode number << 32 with auto-reset — the lockstep collector's stream (RolloutCollector: counter = base + k at
 // its k-th step), so both collectors draw the same actions for the same observations.
 #pragma once
+#include <type_traits>
+
 #include "kernels.h"
 #include "decima.h"
 #include "decima_policy.h"
@@ -123,11 +125,68 @@ __device__ __forceinline__ DpAction decima_decide(
   return act;
 }
 
-template <bool kHelp = false>
+// kTimed: fixed-duration collection (sparksched.h ssim_decima_rollout_timed; the loop's side is rollout.h
+// Pol::kTimedMode). The env's clock, reset schedule and logs are in device memory (`t`), so a launch after the host
+// grew the arena or refilled the schedule continues the call exactly.
+struct DecimaTimedNone {};
+template <bool kTimed>
+using DecimaTimedArgs = std::conditional_t<kTimed, ssim_decima_timed, DecimaTimedNone>;
+template <bool kHelp = false, bool kTimed = false>
 struct DecimaPolicy {
+  static constexpr bool kTimedMode = kTimed;
   const Params* P;
   const uint8_t* obs;
   DecimaRolloutArgs a;
+  DecimaTimedArgs<kTimed> t;
+
+  // The call's simulated time has not elapsed yet (a decision is taken only while elapsed < duration).
+  template <class S>
+  __device__ __forceinline__ bool in_time(const S& s) const {
+    if constexpr (kTimed) return WaveHip::uni(t.clock[2 * (int64_t)s.eid]) < t.duration;
+    return true;
+  }
+  // The env's episode is over: whether its reset schedule has a slot left. If not, the env is flagged (as an env
+  // whose arena is full, can_act) and takes no more decisions in this launch.
+  template <class S>
+  __device__ __forceinline__ bool next_episode(const S& s) const {
+    if constexpr (kTimed) {
+      using W = WaveHip;
+      int32_t* sc = t.sched + 2 * (int64_t)s.eid;
+      if (W::uni(sc[0]) < t.cap_resets) return true;
+      W::sync();
+      if (W::lane() == 0) sc[1] = 1;
+      W::sync();
+      return false;
+    }
+    return true;
+  }
+  // Consumes the env's next schedule slot: logs the sample whose step ended the episode, copies the episode's job
+  // table out (reset() wipes it) and resets the env in place, reseeded, with the slot's time limit.
+  template <class S>
+  __device__ __forceinline__ void reset_episode(S& s, uint8_t* rec) const {
+    if constexpr (kTimed) {
+      using W = WaveHip;
+      const int eid = s.eid;
+      int32_t* sc = t.sched + 2 * (int64_t)eid;
+      const int64_t slot = (int64_t)eid * t.cap_resets + W::uni(sc[0]);
+      const uint64_t seed = W::uni(t.seeds[slot]);
+      const double limit = W::uni(t.limits[slot]);
+      const int last = W::uni(a.smp.cursor[(int64_t)eid * 8]) - 1;
+      const int J = s.JC;
+      for (int j = W::lane(); j < J; j += W::kWidth) {
+        t.ep_arrival[slot * J + j] = s.jtimes(j).tarr;
+        t.ep_completed[slot * J + j] = s.jtimes(j).tdone;
+        t.ep_state[slot * J + j] = s.job(j).state;
+      }
+      W::sync();
+      if (W::lane() == 0) {
+        t.reset_steps[slot] = last;
+        sc[0] = sc[0] + 1;
+      }
+      W::sync();
+      s.reset_sampled(SSIM_RESET_SEED, seed, limit, rec);
+    }
+  }
 
   // Whether act() goes on to choose an action (rollout_body asks before it claims a budgeted decision): not when the
   // collector's episode is over (terminated, truncated by its StochasticTimeLimit, or frozen) or when the sample arena
@@ -184,7 +243,17 @@ struct DecimaPolicy {
     int32_t* ccap = reinterpret_cast<int32_t*>(a.work + a.wl.ccap);
     uint32_t* emask = reinterpret_cast<uint32_t*>(a.work + a.wl.emask);
     int32_t* depth = reinterpret_cast<int32_t*>(a.work + a.wl.depth);
-    const uint64_t ctr = a.counter + (uint64_t)s.h.decisions + (a.autoreset ? (uint64_t)s.h.episode << 32 : 0ull);
+    // (timed: the lockstep async collector's stream, counter + the env's decision index in the call)
+    const uint64_t ctr = kTimed ? a.counter + (uint64_t)cs
+                                : a.counter + (uint64_t)s.h.decisions + (a.autoreset ? (uint64_t)s.h.episode << 32 : 0ull);
+    double before = 0.0;  // (timed) the sample's time: the call's elapsed time before the decision
+    if constexpr (kTimed) {
+      double* ck = t.clock + 2 * (int64_t)eid;
+      before = W::uni(ck[0]);
+      W::sync();
+      if (W::lane() == 0) ck[1] = s.h.wall;  // done() takes the step's duration from it
+      W::sync();
+    }
 #ifdef SSIM_PROFILE
     uint64_t* pprof = s.prof + kPhDecParts;
 #else
@@ -245,7 +314,7 @@ struct DecimaPolicy {
         r.exec_idx = act.exec_idx;
         r.num_exec = act.num_exec;
         r.lgprob = act.lgprob;
-        r.wall_before = s.h.wall;
+        r.wall_before = kTimed ? before : s.h.wall;
         r.reward = 0.0;
         sm.rec[(int64_t)eid * sm.cap_samples + cs] = r;
         cur[0] = cs + 1;
@@ -266,6 +335,14 @@ struct DecimaPolicy {
   __device__ __forceinline__ void done(S& s) const {
     using W = WaveHip;
     const ssim_decima_samples& sm = a.smp;
+    if constexpr (kTimed) {  // elapsed += wall_after - wall_before: one subtraction, then one addition
+      double* ck = t.clock + 2 * (int64_t)s.eid;
+      const double el = W::uni(ck[0]), w0 = W::uni(ck[1]);
+      const double dt = s.h.wall - w0;
+      W::sync();
+      if (W::lane() == 0) ck[0] = el + dt;
+      W::sync();
+    }
     if (sm.rec == nullptr) return;
     const int eid = s.eid;
     const int cs = W::uni(sm.cursor[(int64_t)eid * 8]);
@@ -303,11 +380,12 @@ struct DecimaPolicy {
 // kN / kJ: executor count and job cap as compile-time constants (0 = read from the layout), as kernels.h. kHelp: the
 // workgroup is kDpHelpWaves waves; wave 0 runs the env, the others its exec-score tiles (decima_policy.h), until wave 0
 // publishes kDpHelpExit at the end of its rollout (every path out of rollout_body comes back here).
-template <bool kRes, int kN, int kJ, bool kHelp>
+template <bool kRes, int kN, int kJ, bool kHelp, bool kTimed = false>
 __device__ __forceinline__ void decima_rollout_body(const Params* __restrict__ P, uint8_t* state, uint8_t* obs,
                                                     DecimaRolloutArgs a, int num_steps, int flags,
                                                     const double* __restrict__ limits, uint8_t* reset,
-                                                    int32_t* action_log, int64_t budget, uint64_t* prof_out) {
+                                                    int32_t* action_log, int64_t budget, uint64_t* prof_out,
+                                                    DecimaTimedArgs<kTimed> t = {}) {
   DpHelp* const help = reinterpret_cast<DpHelp*>(g_smem + a.help_off);
   if constexpr (kHelp) {
     const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -319,9 +397,10 @@ __device__ __forceinline__ void decima_rollout_body(const Params* __restrict__ P
   }
   a.autoreset = (flags & SSIM_ROLLOUT_AUTORESET) != 0;
   a.test_reject = (flags & SSIM_ROLLOUT_TEST_REJECT) != 0;
-  const DecimaPolicy<kHelp> pol{P, obs, a};
-  rollout_body<kRes, kN, kJ, 0, DecimaPolicy<kHelp>>(P, state, obs, pol, num_steps, flags, limits, reset, action_log,
-                                                     prof_out, budget, nullptr, !kRes, SSIM_DR_EX_LDS != 0);
+  const DecimaPolicy<kHelp, kTimed> pol{P, obs, a, t};
+  rollout_body<kRes, kN, kJ, 0, DecimaPolicy<kHelp, kTimed>>(P, state, obs, pol, num_steps, flags, limits, reset,
+                                                             action_log, prof_out, budget, nullptr, !kRes,
+                                                             SSIM_DR_EX_LDS != 0);
   if constexpr (kHelp) {
     if (WaveHip::lane() == 0) help->cmd = kDpHelpExit;
     __syncthreads();  // the helpers' barrier A: they read the exit and end
@@ -344,6 +423,15 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, SSIM_DR_THREADS(kHelp))
   decima_rollout_body<kRes, kN, kJ, kHelp>(P, state, obs, a, num_steps, flags, limits, reset, action_log, budget,
                                            prof_out);
 }
+// fixed-duration collection (ssim_decima_rollout_timed): its own kernels, in their own translation units
+// (k_drt_*.hip), so the units above compile exactly as without them
+template <bool kRes, int kN = 0, int kJ = 0, bool kHelp = false>
+__global__ __attribute__((amdgpu_flat_work_group_size(1, SSIM_DR_THREADS(kHelp)), amdgpu_waves_per_eu(SSIM_DR_WAVES(kRes)))) void k_decima_rollout_timed(
+    const Params* __restrict__ P, uint8_t* state, uint8_t* obs, DecimaRolloutArgs a, ssim_decima_timed t, int num_steps,
+    int flags, uint8_t* reset, int32_t* action_log, uint64_t* prof_out) {
+  decima_rollout_body<kRes, kN, kJ, kHelp, true>(P, state, obs, a, num_steps, flags, nullptr, reset, action_log, 0,
+                                                 prof_out, t);
+}
 
 using DecimaRolloutFn = void (*)(const Params*, uint8_t*, uint8_t*, DecimaRolloutArgs, int, int, const double*,
                                  uint8_t*, int32_t*, int64_t, uint64_t*);
@@ -353,6 +441,13 @@ struct DecimaRolloutSet {
   const char* name;      // the translation unit (ssim_debug_kernel_name)
   int waves = 1;         // waves per env's workgroup (kDpHelpWaves: the exec-score helpers)
 };
+using DecimaTimedFn = void (*)(const Params*, uint8_t*, uint8_t*, DecimaRolloutArgs, ssim_decima_timed, int, int,
+                               uint8_t*, int32_t*, uint64_t*);
+// one per k_dr_*.hip unit, with that unit's compile definitions
+DecimaTimedFn decima_timed_hbm();    // k_drt_hbm.hip
+DecimaTimedFn decima_timed_hbm50();  // k_drt_hbm50.hip
+DecimaTimedFn decima_timed_lds();    // k_drt_lds.hip
+DecimaTimedFn decima_timed_lds50();  // k_drt_lds50.hip
 DecimaRolloutSet decima_rollout_hbm();    // k_dr_hbm.hip
 DecimaRolloutSet decima_rollout_hbm50();  // k_dr_hbm50.hip: 50 executors / 200 jobs
 DecimaRolloutSet decima_rollout_lds();    // k_dr_lds.hip

@@ -1,0 +1,7 @@
+// k_drt_hbm.hip — fixed-duration persistent Decima rollout (decima_rollout.h k_decima_rollout_timed): hot block in HBM,
+// any shape. Compiled as k_dr_hbm.hip is, in its own unit so that one is unchanged by it.
+#define SSIM_OPAQUE_LANE 1
+#define SSIM_EV_PAGES_GENERIC 2
+#include "decima_rollout.h"
+
+DecimaTimedFn decima_timed_hbm() { return k_decima_rollout_timed<false>; }

@@ -1,0 +1,6 @@
+// k_drt_hbm50.hip — fixed-duration persistent Decima rollout (decima_rollout.h k_decima_rollout_timed): hot block in
+// HBM, 50 executors / 200 jobs. Compiled as k_dr_hbm50.hip is, in its own unit so that one is unchanged by it.
+#define SSIM_OPAQUE_LANE 1
+#include "decima_rollout.h"
+
+DecimaTimedFn decima_timed_hbm50() { return k_decima_rollout_timed<false, 50, 200>; }

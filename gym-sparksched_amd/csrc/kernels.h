@@ -115,7 +115,8 @@ __device__ __forceinline__ void rollout_body(const Params* __restrict__ P, uint8
     if (num_steps <= 0) return;
   }
   const bool autoreset = (flags & SSIM_ROLLOUT_AUTORESET) != 0;
-  if (!autoreset && action_log == nullptr && env_idle(P, state, eid)) return;
+  // (fixed-duration collection resets a terminated env from its schedule: it is not idle)
+  if (!autoreset && !Pol::kTimedMode && action_log == nullptr && env_idle(P, state, eid)) return;
   // Shared budget (budget > 0): decisions are claimed from one device counter in chunks sized to what is
   // left (guided self-scheduling: 8 early, 1 at the end), so the launch ends within ~one decision of the
   // budget running out instead of waiting for the env with the most expensive K decisions. With
@@ -143,7 +144,10 @@ __device__ __forceinline__ void rollout_body(const Params* __restrict__ P, uint8
   s.prof_set(kTLoaded, WaveHip::realtime());
 #endif
   const auto reset_in_place = [&](Sim<WaveHip, kN, kJ, kS>& x) {
-    x.reset_sampled(SSIM_RESET_CONTINUE, 0ull, limit, rec);
+    if constexpr (Pol::kTimedMode)
+      pol.reset_episode(x, rec);  // reseeded, from the env's reset schedule (decima_rollout.h)
+    else
+      x.reset_sampled(SSIM_RESET_CONTINUE, 0ull, limit, rec);
   };
   rollout_loop(s, pol, stop, c, B, eid, num_steps, autoreset, action_log, reset_in_place);
   if (c.granted > 0) stop.give_back(c.granted);  // a chunk the wave could not use (its step cap or episode end)

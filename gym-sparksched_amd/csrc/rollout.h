@@ -20,6 +20,7 @@ struct NoBudget : NoStop {
 // a decision this launch started has completed (its observation written), `rejected` when the env refused the action
 // act() chose (the env is then frozen with SSIM_ERR_INVARIANT).
 struct HeuristicPolicy {  // fair / FIFO / random (policy.h)
+  static constexpr bool kTimedMode = false;  // (fixed-duration collection: decima_rollout.h DecimaPolicy)
   int kind;
   uint64_t seed;
   // whether act() would choose an action (checked before a budget claim, so a claim is never spent on an env whose
@@ -59,6 +60,18 @@ __device__ __forceinline__ void rollout_loop(SimT& s, const Pol& pol, const Stop
     const uint64_t t0 = W::clock();
 #endif
     s.load_header();
+    if constexpr (Pol::kTimedMode) {
+      // Fixed-duration collection (RolloutWorkerAsync.collect_rollout, rollout_worker.py:160-206): a finished episode
+      // is reset first, from the next slot of the env's reset schedule (reset_env), even when its last step carried
+      // the call's elapsed time past the duration; only then is the elapsed time checked. Both stops are plain
+      // breaks, like every other way out of the loop.
+      if (s.h.num_jobs > 0 && !s.frozen() && (s.h.terminated || s.h.wall >= s.h.time_limit) && !s.pending()) {
+        if (!pol.next_episode(s)) break;  // the schedule is used up: flagged, the host refills it and launches again
+        reset_env(s);
+        continue;
+      }
+      if (!s.pending() && !pol.in_time(s)) break;  // the call's simulated time has elapsed
+    }
     // episode over (terminated, or truncated by the time limit): reset(seed=None) in place, before anything else
     // (one call site for the whole loop). A preemptible budget launch resets only when it holds a claimed
     // decision for the new episode: an episode that ends as the budget runs out is reset at the start of the

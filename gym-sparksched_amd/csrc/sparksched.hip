@@ -654,37 +654,37 @@ extern "C" int64_t ssim_decima_workspace_bytes(const ssim_handle* h) {
   return decima_work(h->params.L).total;
 }
 
-extern "C" int ssim_decima_rollout(ssim_handle* h, const float* params, int32_t num_params, float num_tasks_scale,
-                                   float work_scale, uint64_t seed, uint64_t counter, int32_t max_steps,
-                                   int64_t total_decisions, int32_t flags, const double* time_limits, void* workspace,
-                                   int64_t workspace_bytes, const ssim_decima_samples* samples, int32_t* action_log,
-                                   void* stream) {
-  if (h == nullptr || params == nullptr || workspace == nullptr || max_steps < 0 || total_decisions < 0)
-    return set_err(SSIM_E_ARG, "ssim_decima_rollout: bad argument");
+// The checks and launch arguments ssim_decima_rollout and ssim_decima_rollout_timed share (`who` names the entry in
+// messages): the policy weights packed on `stream`, the workspace layout, the sample arena.
+static int decima_rollout_args(const char* who, ssim_handle* h, const float* params, int32_t num_params,
+                               float num_tasks_scale, float work_scale, uint64_t seed, uint64_t counter,
+                               void* workspace, int64_t workspace_bytes, const ssim_decima_samples* samples,
+                               void* stream, DecimaRolloutArgs* out) {
   if (num_params != kDecimaParams)
-    return set_err(SSIM_E_ARG, "ssim_decima_rollout: %d parameters, the fused kernel implements the "
-                   "decima_tpch.yaml architecture (%d)", num_params, kDecimaParams);
-  if ((flags & ~(SSIM_ROLLOUT_AUTORESET | SSIM_ROLLOUT_PREEMPT | SSIM_ROLLOUT_WARMUP | SSIM_ROLLOUT_TEST_REJECT)) != 0)
-    return set_err(SSIM_E_ARG, "ssim_decima_rollout: unknown flags 0x%x", flags);
-  if ((flags & SSIM_ROLLOUT_PREEMPT) && total_decisions <= 0)
-    return set_err(SSIM_E_ARG, "ssim_decima_rollout: SSIM_ROLLOUT_PREEMPT needs a decision budget");
-  if ((flags & SSIM_ROLLOUT_AUTORESET) && !(h->params.C.job_arrival_gap > 0.0))
-    return set_err(SSIM_E_ARG, "ssim_decima_rollout: auto-reset needs job_arrival_gap in the config");
+    return set_err(SSIM_E_ARG, "%s: %d parameters, the fused kernel implements the "
+                   "decima_tpch.yaml architecture (%d)", who, num_params, kDecimaParams);
   const ssim_layout& L = h->params.L;
   if (h->params.C.max_stages > kDecimaMaxDepth)
-    return set_err(SSIM_E_ARG, "ssim_decima_rollout: max_stages %d > %d (edge-mask word)", h->params.C.max_stages,
+    return set_err(SSIM_E_ARG, "%s: max_stages %d > %d (edge-mask word)", who, h->params.C.max_stages,
                    kDecimaMaxDepth);
   if (L.num_executors > 64 * kDpExecChunks)
-    return set_err(SSIM_E_ARG, "ssim_decima_rollout: more than %d executors", 64 * kDpExecChunks);
+    return set_err(SSIM_E_ARG, "%s: more than %d executors", who, 64 * kDpExecChunks);
   // (the global plan's agg rows, stage_cap x 16 floats, hold the N exec scores too: decima_lds_plan)
   if (L.stage_cap < (L.num_executors + kDpEmb - 1) / kDpEmb)
-    return set_err(SSIM_E_ARG, "ssim_decima_rollout: stage cap %d below ceil(%d executors / %d): the policy plan "
-                   "cannot hold the exec scores", L.stage_cap, L.num_executors, kDpEmb);
+    return set_err(SSIM_E_ARG, "%s: stage cap %d below ceil(%d executors / %d): the policy plan "
+                   "cannot hold the exec scores", who, L.stage_cap, L.num_executors, kDpEmb);
   const DecimaWork wl = decima_work(L);
   if (workspace_bytes < wl.total)
-    return set_err(SSIM_E_ARG, "ssim_decima_rollout: workspace of %lld B, needs %lld (ssim_decima_workspace_bytes)",
+    return set_err(SSIM_E_ARG, "%s: workspace of %lld B, needs %lld (ssim_decima_workspace_bytes)", who,
                    (long long)workspace_bytes, (long long)wl.total);
   DecimaRolloutArgs a{};
+  if (samples != nullptr) {
+    const ssim_decima_samples& sm = *samples;
+    if (sm.cursor == nullptr || sm.rec == nullptr || sm.nodes == nullptr || sm.edges == nullptr || sm.dags == nullptr ||
+        sm.cap_samples <= 0 || sm.cap_nodes < 0 || sm.cap_edges < 0 || sm.cap_dags < 0)
+      return set_err(SSIM_E_ARG, "%s: incomplete sample arena", who);
+    a.smp = sm;
+  }
   a.weights = reinterpret_cast<const dp_f32x4*>(static_cast<uint8_t*>(workspace) + wl.packed);
   a.work = static_cast<uint8_t*>(workspace);
   {
@@ -696,13 +696,30 @@ extern "C" int ssim_decima_rollout(ssim_handle* h, const float* params, int32_t 
   a.work_scale = work_scale;
   a.seed = seed;
   a.counter = counter;
-  if (samples != nullptr) {
-    const ssim_decima_samples& sm = *samples;
-    if (sm.cursor == nullptr || sm.rec == nullptr || sm.nodes == nullptr || sm.edges == nullptr || sm.dags == nullptr ||
-        sm.cap_samples <= 0 || sm.cap_nodes < 0 || sm.cap_edges < 0 || sm.cap_dags < 0)
-      return set_err(SSIM_E_ARG, "ssim_decima_rollout: incomplete sample arena");
-    a.smp = sm;
+  *out = a;
+  return SSIM_OK;
+}
+
+extern "C" int ssim_decima_rollout(ssim_handle* h, const float* params, int32_t num_params, float num_tasks_scale,
+                                   float work_scale, uint64_t seed, uint64_t counter, int32_t max_steps,
+                                   int64_t total_decisions, int32_t flags, const double* time_limits, void* workspace,
+                                   int64_t workspace_bytes, const ssim_decima_samples* samples, int32_t* action_log,
+                                   void* stream) {
+  if (h == nullptr || params == nullptr || workspace == nullptr || max_steps < 0 || total_decisions < 0)
+    return set_err(SSIM_E_ARG, "ssim_decima_rollout: bad argument");
+  if ((flags & ~(SSIM_ROLLOUT_AUTORESET | SSIM_ROLLOUT_PREEMPT | SSIM_ROLLOUT_WARMUP | SSIM_ROLLOUT_TEST_REJECT)) != 0)
+    return set_err(SSIM_E_ARG, "ssim_decima_rollout: unknown flags 0x%x", flags);
+  if ((flags & SSIM_ROLLOUT_PREEMPT) && total_decisions <= 0)
+    return set_err(SSIM_E_ARG, "ssim_decima_rollout: SSIM_ROLLOUT_PREEMPT needs a decision budget");
+  if ((flags & SSIM_ROLLOUT_AUTORESET) && !(h->params.C.job_arrival_gap > 0.0))
+    return set_err(SSIM_E_ARG, "ssim_decima_rollout: auto-reset needs job_arrival_gap in the config");
+  DecimaRolloutArgs a{};
+  {
+    const int rc = decima_rollout_args("ssim_decima_rollout", h, params, num_params, num_tasks_scale, work_scale, seed,
+                                       counter, workspace, workspace_bytes, samples, stream, &a);
+    if (rc != SSIM_OK) return rc;
   }
+  const ssim_layout& L = h->params.L;
   const DecimaRolloutSet ks = pick_decima(h->params);
   const DecimaRolloutFn fn = (flags & SSIM_ROLLOUT_WARMUP) ? ks.rollout_warmup : ks.rollout;
   const DecimaLdsPlan pl = decima_lds_plan(h->params, ks);
@@ -720,6 +737,58 @@ extern "C" int ssim_decima_rollout(ssim_handle* h, const float* params, int32_t 
   const int rc2 = hip_check(hipGetLastError(), "k_decima_rollout launch");
   if (rc2 == SSIM_OK && total_decisions > 0) h->ticket_slot ^= 1;
   return rc2;
+}
+
+// The fixed-duration kernel of the unit pick_decima selects (same layout rule, same LDS plan, same waves).
+static DecimaTimedFn pick_decima_timed(const Params& p) {
+  return p.O.lds_resident                        ? (decima_shape(p) && !generic_forced() ? decima_timed_lds50()
+                                                                                        : decima_timed_lds())
+         : !decima_shape(p) || generic_forced() ? decima_timed_hbm()
+                                                : decima_timed_hbm50();
+}
+
+extern "C" int ssim_decima_rollout_timed(ssim_handle* h, const float* params, int32_t num_params,
+                                         float num_tasks_scale, float work_scale, uint64_t seed, uint64_t counter,
+                                         int32_t max_steps, int64_t total_decisions, int32_t flags,
+                                         const double* time_limits, void* workspace, int64_t workspace_bytes,
+                                         const ssim_decima_samples* samples, const ssim_decima_timed* timed,
+                                         int32_t* action_log, void* stream) {
+  if (h == nullptr || params == nullptr || workspace == nullptr || max_steps < 0)
+    return set_err(SSIM_E_ARG, "ssim_decima_rollout_timed: bad argument");
+  if ((flags & (SSIM_ROLLOUT_AUTORESET | SSIM_ROLLOUT_PREEMPT | SSIM_ROLLOUT_WARMUP)) != 0 || total_decisions != 0 ||
+      time_limits != nullptr)
+    return set_err(SSIM_E_ARG, "ssim_decima_rollout_timed: does not combine with SSIM_ROLLOUT_AUTORESET / PREEMPT / "
+                   "WARMUP, a decision budget or time_limits (flags 0x%x)", flags);
+  if ((flags & ~SSIM_ROLLOUT_TEST_REJECT) != 0)
+    return set_err(SSIM_E_ARG, "ssim_decima_rollout_timed: unknown flags 0x%x", flags);
+  if (samples == nullptr) return set_err(SSIM_E_ARG, "ssim_decima_rollout_timed: needs a sample arena");
+  if (timed == nullptr) return set_err(SSIM_E_ARG, "ssim_decima_rollout_timed: null timed argument");
+  const ssim_decima_timed& t = *timed;
+  if (t.cap_resets <= 0) return set_err(SSIM_E_ARG, "ssim_decima_rollout_timed: cap_resets %d <= 0", t.cap_resets);
+  if (t.clock == nullptr || t.seeds == nullptr || t.limits == nullptr || t.sched == nullptr ||
+      t.reset_steps == nullptr || t.ep_arrival == nullptr || t.ep_completed == nullptr || t.ep_state == nullptr)
+    return set_err(SSIM_E_ARG, "ssim_decima_rollout_timed: incomplete timed argument (null array)");
+  if (!(t.duration >= 0.0)) return set_err(SSIM_E_ARG, "ssim_decima_rollout_timed: duration must be >= 0");
+  if (!(h->params.C.job_arrival_gap > 0.0))
+    return set_err(SSIM_E_ARG, "ssim_decima_rollout_timed: in-place resets need job_arrival_gap in the config");
+  DecimaRolloutArgs a{};
+  {
+    const int rc = decima_rollout_args("ssim_decima_rollout_timed", h, params, num_params, num_tasks_scale, work_scale,
+                                       seed, counter, workspace, workspace_bytes, samples, stream, &a);
+    if (rc != SSIM_OK) return rc;
+  }
+  const DecimaRolloutSet ks = pick_decima(h->params);  // (the plan and the waves of the timed kernel's sibling unit)
+  const DecimaTimedFn fn = pick_decima_timed(h->params);
+  const DecimaLdsPlan pl = decima_lds_plan(h->params, ks);
+  a.plan_cap = pl.cap;
+  a.plan_off = pl.off;
+  a.help_off = pl.help_off;
+  const int rc = lds_opt_in((const void*)fn, pl.lds);
+  if (rc != SSIM_OK) return rc;
+  hipLaunchKernelGGL(fn, dim3(h->params.L.num_envs), dim3(64 * ks.waves), (size_t)pl.lds, (hipStream_t)stream,
+                     dparams(h), h->state, h->obs, a, t, max_steps, flags, h->reset, action_log, h->prof_next);
+  h->prof_next = nullptr;
+  return hip_check(hipGetLastError(), "k_decima_rollout_timed launch");
 }
 
 extern "C" const char* ssim_last_error(void) { return g_err; }

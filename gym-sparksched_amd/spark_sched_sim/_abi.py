@@ -114,6 +114,16 @@ class SsimDecimaSamples(ct.Structure):
                 ("cap_edges", ct.c_int32), ("cap_dags", ct.c_int32)]
 
 
+class SsimDecimaTimed(ct.Structure):
+    """ssim_decima_timed: the fixed-duration rollout's per-env clock, reset schedule and reset logs (device pointers)."""
+    _fields_ = [("duration", ct.c_double), ("clock", ct.c_void_p), ("seeds", ct.c_void_p), ("limits", ct.c_void_p),
+                ("sched", ct.c_void_p), ("reset_steps", ct.c_void_p), ("ep_arrival", ct.c_void_p),
+                ("ep_completed", ct.c_void_p), ("ep_state", ct.c_void_p), ("cap_resets", ct.c_int32),
+                ("pad", ct.c_int32)]
+
+
+SCHED_USED, SCHED_EXHAUSTED = 0, 1  # ssim_decima_timed.sched words
+
 # ssim_decima_sample (64 B): int32 fields, then float lgprob, then f64 wall_before / reward
 SAMPLE_I32 = ["num_nodes", "num_edges", "num_dags", "depth", "node_off", "edge_off", "dag_off", "stage_idx",
               "job_idx", "exec_idx", "num_exec"]

@@ -413,7 +413,29 @@ class DeviceEngine:
             None if st is None else ct.byref(st), None if action_log is None else action_log.data_ptr(),
             self._stream()), "ssim_decima_rollout")
 
-    def decima_features_np(self, num_tasks_scale: float = 200.0, work_scale: float = 1e5) -> dict:
+    def decima_rollout_timed(self, params, seed: int, counter: int, max_steps: int, samples, timed,
+                             flags: int = 0, total_decisions: int = 0, time_limits=None, action_log=None,
+                             num_tasks_scale: float = 200.0, work_scale: float = 1e5, tensors=()):
+        """ssim_decima_rollout_timed: the persistent Decima rollout stopped per env on the simulated time elapsed in
+        the call, with reseeded in-place resets from a host-filled schedule. samples: a DecimaSampleArena (required by
+        the library; None is passed through so its refusal can be tested); timed: an _abi.SsimDecimaTimed whose
+        device arrays are `tensors` (kept alive with the launch, as `params` is). flags / total_decisions /
+        time_limits exist to be refused: the mode combines with none of them."""
+        ws = self.decima_workspace()
+        tl = None
+        if time_limits is not None:
+            tl = self.torch.as_tensor(np.asarray(time_limits, dtype=np.float64).reshape(self.num_envs),
+                                      device=self.device) if not hasattr(time_limits, "data_ptr") else time_limits
+        st = samples.struct() if samples is not None else None
+        self._keep_dr = (params, tl, st, timed, tuple(tensors))
+        self._native.check(self._native.lib().ssim_decima_rollout_timed(
+            self.handle, params.data_ptr(), params.numel(), float(num_tasks_scale), float(work_scale),
+            int(seed) & (2**64 - 1), int(counter) & (2**64 - 1), int(max_steps), int(total_decisions), int(flags),
+            None if tl is None else tl.data_ptr(), ws.data_ptr(), ws.numel(),
+            None if st is None else ct.byref(st), None if timed is None else ct.byref(timed),
+            None if action_log is None else action_log.data_ptr(), self._stream()), "ssim_decima_rollout_timed")
+
+    def decima_features_np(self,num_tasks_scale: float = 200.0, work_scale: float = 1e5) -> dict:
         return {k: x.cpu().numpy() for k, x in self.decima_features(num_tasks_scale, work_scale).items()}
 
     def job_times_np(self):

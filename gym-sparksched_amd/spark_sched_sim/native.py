@@ -55,6 +55,8 @@ def lib() -> ct.CDLL:
     L.ssim_debug_decima_plan.restype = ct.c_int
     L.ssim_decima_rollout.argtypes = [vp, vp, i32, ct.c_float, ct.c_float, u64, u64, i32, ct.c_int64, i32, vp, vp,
                                       ct.c_int64, vp, vp, vp]
+    L.ssim_decima_rollout_timed.argtypes = [vp, vp, i32, ct.c_float, ct.c_float, u64, u64, i32, ct.c_int64, i32, vp,
+                                            vp, ct.c_int64, vp, vp, vp, vp]
     L.ssim_last_error.restype = ct.c_char_p
     L.ssim_build_id.restype = ct.c_char_p
     L.ssim_debug_set_trace.argtypes = [vp, vp, i32, i32, vp, vp]
@@ -84,7 +86,8 @@ def lib() -> ct.CDLL:
     L.ssim_discounted_returns.restype = ct.c_int
     for name in ("ssim_layout_for", "ssim_create", "ssim_destroy", "ssim_reset", "ssim_step", "ssim_policy",
                  "ssim_rollout", "ssim_rollout_ex", "ssim_rollout_budget", "ssim_rollout_steps", "ssim_reset_sampled",
-                 "ssim_job_times", "ssim_decima_features", "ssim_decima_policy", "ssim_decima_rollout"):
+                 "ssim_job_times", "ssim_decima_features", "ssim_decima_policy", "ssim_decima_rollout",
+                 "ssim_decima_rollout_timed"):
         getattr(L, name).restype = ct.c_int
     _lib = L
     return L
@@ -99,7 +102,7 @@ EXPORTED_SYMBOLS = ["ssim_layout_for", "ssim_create", "ssim_destroy", "ssim_rese
                     "ssim_rollout", "ssim_rollout_ex", "ssim_rollout_budget", "ssim_rollout_steps", "ssim_reset_sampled",
                     "ssim_job_times",
                     "ssim_decima_features", "ssim_decima_policy", "ssim_decima_workspace_bytes", "ssim_decima_rollout",
-                    "ssim_decima_rollout_lds_bytes", "ssim_debug_decima_plan",
+                    "ssim_decima_rollout_timed", "ssim_decima_rollout_lds_bytes", "ssim_debug_decima_plan",
                     "ssim_last_error", "ssim_build_id", "ssim_debug_set_trace", "ssim_debug_set_trace_ex",
                     "ssim_debug_kernel_name", "ssim_linear_fwd",
                     "ssim_linear_wgrad_parts", "ssim_linear_wgrad", "ssim_mlp3_supported", "ssim_mlp3_fwd",

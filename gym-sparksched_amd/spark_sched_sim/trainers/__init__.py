@@ -5,5 +5,6 @@ Restates trainers/{trainer,ppo,rollout_worker}.py and trainers/utils/{returns_ca
 
 from .ppo import DECIMA_TPCH, PPO, make_trainer  # noqa: F401
 from .returns import Baseline, ReturnsCalculator  # noqa: F401
-from .rollouts import (AsyncRolloutCollector, ArenaRolloutBuffer, DecimaSampleArena, DeviceRolloutCollector,  # noqa: F401
-                       GpuRolloutBuffer, RolloutCollector)
+from .rollouts import (AsyncRolloutCollector, ArenaRolloutBuffer, DecimaSampleArena,  # noqa: F401
+                       DeviceAsyncRolloutCollector, DeviceRolloutCollector, GpuRolloutBuffer, ResetSchedule,
+                       RolloutCollector)

@@ -32,7 +32,8 @@ import torch
 from ..distributed import all_gather_var, gather_var, split_rows
 from ..schedulers.decima import DagBatch, DecimaScheduler, cat_batches, learner_counts, minibatch_plans, select_envs
 from .returns import Baseline, ReturnsCalculator
-from .rollouts import AsyncRolloutCollector, DeviceRolloutCollector, RolloutCollector
+from .rollouts import (AsyncRolloutCollector, DeviceAsyncRolloutCollector, DeviceRolloutCollector,
+                       RolloutCollector)
 
 EPS = 1e-8  # ppo.py:13
 _BATCH_TENSORS = ["x", "edge_index", "edge_bits", "env_levels", "ptr", "node_dag", "node_env", "dag_env", "obs_ptr",
@@ -128,6 +129,14 @@ class PPO:
             self.collector = AsyncRolloutCollector(self.engine, self.scheduler, self.rollout_duration, base,
                                                    self.num_sequences, mean_time_limit=self.mean_time_limit,
                                                    seed=rseed, row_offset=self.row_lo)
+            # device engines: each call in persistent launches (same actions, resets and statistics,
+            # csrc/decima_rollout.h timed mode); train_cfg["lockstep_rollouts"] keeps the per-decision collector
+            if (self.collector.on_device and self.collector.fused and hasattr(self.engine, "decima_rollout_timed")
+                    and not train_cfg.get("lockstep_rollouts", False)):
+                self.collector = DeviceAsyncRolloutCollector(self.engine, self.scheduler, self.rollout_duration, base,
+                                                             self.num_sequences,
+                                                             mean_time_limit=self.mean_time_limit, seed=rseed,
+                                                             row_offset=self.row_lo)
         else:
             self.collector = RolloutCollector(self.engine, self.scheduler, seed=rseed, row_offset=self.row_lo)
             # device engines: the whole collection in one persistent launch (same actions, csrc/decima_rollout.h);

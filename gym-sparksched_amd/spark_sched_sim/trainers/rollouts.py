@@ -468,3 +468,153 @@ class AsyncRolloutCollector(RolloutCollector):
             alive = alive & (elapsed < self.rollout_duration)
         buf.final_wall = elapsed
         return buf
+
+
+class ResetSchedule:
+    """The next resets of every worker row, precomputed for the device: slot k of row e holds the seed
+    base_seeds[e] + seed_step * (reset_count[e] + k) (rollout_worker.py:118-120) and the StochasticTimeLimit draw
+    `sampler.sample(e, seed)` would return for it if called once per reset, in order. The draws run on COPIES of the
+    rows' RandomStates (sample() continues the previous state when the seed is 0), so slots that are never consumed
+    leave the sampler as it was; `commit` replays the consumed slots on the sampler itself."""
+
+    def __init__(self, base_seeds, seed_step: int, sampler: StochasticTimeLimitSampler | None):
+        self.base_seeds = np.asarray(base_seeds, dtype=np.int64).reshape(-1)
+        self.seed_step = int(seed_step)
+        self.sampler = sampler
+
+    def fill(self, reset_count, cap_resets: int):
+        """(seeds uint64 [B, cap_resets], limits float64 [B, cap_resets]) from each row's reset_count onward."""
+        B = len(self.base_seeds)
+        seeds = np.zeros((B, cap_resets), dtype=np.uint64)
+        limits = np.full((B, cap_resets), np.inf)
+        for e in range(B):
+            rng = None
+            for k in range(cap_resets):
+                seed = int(self.base_seeds[e] + self.seed_step * (int(reset_count[e]) + k))
+                seeds[e, k] = seed
+                if self.sampler is None:
+                    continue
+                if seed:  # StochasticTimeLimitSampler.sample: a non-zero seed reseeds, 0 continues
+                    rng = np.random.RandomState(seed)
+                elif rng is None:
+                    rng = np.random.RandomState()
+                    rng.set_state(self.sampler.rngs[e].get_state())
+                limits[e, k] = float(rng.exponential(self.sampler.mean))
+        return seeds, limits
+
+    def commit(self, env: int, seeds, limits) -> None:
+        """The row consumed these slots (in order): advance the sampler through them."""
+        if self.sampler is None:
+            return
+        for seed, limit in zip(seeds, limits):
+            got = self.sampler.sample(int(env), int(seed))
+            if got != float(limit):
+                raise AssertionError(f"row {env}: scheduled time limit {limit!r}, the sampler draws {got!r}")
+
+
+class DeviceAsyncRolloutCollector(AsyncRolloutCollector):
+    """AsyncRolloutCollector in persistent launches (ssim_decima_rollout_timed, csrc/decima_rollout.h): each env's wave
+    runs its own loop (features, fused Decima policy, step) until `rollout_duration` ms of simulated time have elapsed
+    in the call, resets a finished episode in place from a reset schedule the host precomputes (ResetSchedule:
+    `cap_resets` slots per row) and leaves every decision in a DecimaSampleArena. One launch per call unless a row
+    uses up its slots (the schedule is refilled) or the arena is full (it grows); the env continues where it stopped.
+    Same sampling stream, seeds, limits, reset steps and row statistics as the lockstep collector."""
+
+    def __init__(self, engine, policy, rollout_duration: float, base_seeds, seed_step: int,
+                 mean_time_limit: float | None = None, cap_resets: int = 4, cap_samples: int = 1024,
+                 cap_nodes: int = 1 << 16, cap_edges: int = 1 << 16, cap_dags: int = 1 << 14, **kw):
+        super().__init__(engine, policy, rollout_duration, base_seeds, seed_step, mean_time_limit=mean_time_limit, **kw)
+        if not (self.on_device and self.fused and hasattr(engine, "decima_rollout_timed")):
+            raise ValueError("DeviceAsyncRolloutCollector needs a DeviceEngine and the decima_tpch.yaml architecture")
+        if cap_resets < 1:
+            raise ValueError("cap_resets must be >= 1")
+        B, J, dev = engine.num_envs, engine.cfg.job_cap, engine.device
+        self.cap_resets = int(cap_resets)
+        self.arena = DecimaSampleArena(B, dev, cap_samples, cap_nodes, cap_edges, cap_dags)
+        self.schedule = ResetSchedule(self.base_seeds, self.seed_step, self.limits)
+        R = self.cap_resets
+        self.clock = torch.zeros((B, 2), dtype=torch.float64, device=dev)
+        self.sched_seeds = torch.zeros((B, R), dtype=torch.int64, device=dev)
+        self.sched_limits = torch.zeros((B, R), dtype=torch.float64, device=dev)
+        self.sched = torch.zeros((B, 2), dtype=torch.int32, device=dev)
+        self.reset_steps = torch.zeros((B, R), dtype=torch.int32, device=dev)
+        self.ep_arrival = torch.zeros((B, R, J), dtype=torch.float64, device=dev)
+        self.ep_completed = torch.zeros((B, R, J), dtype=torch.float64, device=dev)
+        self.ep_state = torch.zeros((B, R, J), dtype=torch.int32, device=dev)
+        self.launches = 0  # kernel launches, schedule refills and arena growths so far
+        self.refills = 0
+        self.growths = 0
+        self.total_resets = 0  # in-place resets so far
+
+    def _timed(self) -> _abi.SsimDecimaTimed:
+        return _abi.SsimDecimaTimed(self.rollout_duration, self.clock.data_ptr(), self.sched_seeds.data_ptr(),
+                                    self.sched_limits.data_ptr(), self.sched.data_ptr(), self.reset_steps.data_ptr(),
+                                    self.ep_arrival.data_ptr(), self.ep_completed.data_ptr(),
+                                    self.ep_state.data_ptr(), self.cap_resets, 0)
+
+    def _fill_schedule(self):
+        seeds, limits = self.schedule.fill(self.reset_count, self.cap_resets)
+        self.sched_seeds.copy_(torch.from_numpy(seeds.view(np.int64)))
+        self.sched_limits.copy_(torch.from_numpy(limits))
+        self.sched.zero_()
+        return seeds, limits
+
+    def _consume(self, used: np.ndarray, seeds, limits, resets: list) -> None:
+        """The slots the launch consumed, in slot order per row: the reset steps, the ended episodes' completions into
+        the rows' duration windows (as AsyncRolloutCollector._reset's flush), the sampler and reset_count."""
+        steps = self.reset_steps.cpu().numpy()
+        ta, tc, st = self.ep_arrival.cpu().numpy(), self.ep_completed.cpu().numpy(), self.ep_state.cpu().numpy()
+        for e in np.flatnonzero(used):
+            n = int(used[e])
+            for k in range(n):
+                resets.append((int(e), int(steps[e, k])))
+                self.stats.windows[e].extend(self.stats._completed(ta[e], tc[e], st[e], k))
+            self.schedule.commit(e, seeds[e, :n], limits[e, :n])
+            self.reset_count[e] += n
+            self.total_resets += n
+
+    @torch.no_grad()
+    def collect(self, generator=None, max_steps: int = 10**9) -> "ArenaRolloutBuffer":
+        self.calls += 1
+        eng = self.engine
+        if self.next_wall is None:  # first call: reset every worker on the host path (reset 0 of every row)
+            self._reset(np.arange(eng.num_envs))
+        params = self.policy.packed_params(eng.device)
+        ctr = ((self.calls << 32) + 1 + self.row_offset * 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF
+        self.arena.clear()
+        self.clock.zero_()
+        seeds, limits = self._fill_schedule()
+        timed = self._timed()
+        keep = (self.clock, self.sched_seeds, self.sched_limits, self.sched, self.reset_steps, self.ep_arrival,
+                self.ep_completed, self.ep_state)
+        steps = int(min(max_steps, 2**31 - 1))
+        resets: list = []
+        while True:
+            eng.decima_rollout_timed(params, self.seed, ctr, steps, self.arena, timed, tensors=keep,
+                                     num_tasks_scale=self.scales[0], work_scale=self.scales[1])
+            self.launches += 1
+            cur = self.arena.cursor.cpu().numpy()
+            sc = self.sched.cpu().numpy()
+            used = sc[:, _abi.SCHED_USED]
+            if used.any():
+                self._consume(used, seeds, limits, resets)
+            full = (cur[:, _abi.CUR_FULL] != 0).any()
+            out = (sc[:, _abi.SCHED_EXHAUSTED] != 0).any()
+            if not (full or out):
+                break
+            if full:
+                self.arena.grow(cur)
+                self.growths += 1
+            if out:
+                self.refills += 1
+            if used.any():  # the next launch's slots continue each row's seed stream
+                seeds, limits = self._fill_schedule()
+        err = eng.views["counts"][:, _abi.OC_ERR].cpu().numpy() & _abi.SSIM_ERR_STICKY
+        if err.any():  # e.g. an action the engine refused (frozen with SSIM_ERR_INVARIANT): its samples are invalid
+            bad = np.flatnonzero(err)
+            raise RuntimeError(f"decima rollout: envs {bad[:8].tolist()} frozen with error bits "
+                               f"{[hex(int(x)) for x in err[bad[:8]]]}")
+        self.next_wall = eng.views["wall_time"].double().clone()
+        buf = self.arena.buffer(self.clock[:, 0].clone())  # times are elapsed times: the final one closes each row
+        buf.resets = sorted(resets, key=lambda r: (r[1], r[0]))  # (env, step) in the lockstep loop's order
+        return buf

@@ -323,6 +323,44 @@ int ssim_decima_rollout(ssim_handle* h, const float* params, int32_t num_params,
                         int32_t flags, const double* time_limits, void* workspace, int64_t workspace_bytes,
                         const ssim_decima_samples* samples, int32_t* action_log, void* stream);
 
+/* ---- fixed-duration Decima rollouts -------------------------------------------------------------------------
+ * ssim_decima_rollout_timed restates trainers/rollout_worker.py:160-206 (RolloutWorkerAsync.collect_rollout) per env in
+ * one launch: an env keeps its episode across calls and takes decisions while the simulated time elapsed in this call
+ * is below `duration`; an env whose episode ends (terminated, or wall_time >= its time limit) is reset in place with
+ * reset(seed) semantics (as ssim_reset_sampled SSIM_RESET_SEED) from the next slot of its reset schedule, which the
+ * host fills with the worker's seed stream and its StochasticTimeLimit draws, and goes on. After a step,
+ * elapsed += wall_after - wall_before (wall_before is 0 after a reset). Device arrays, caller-allocated: */
+typedef struct ssim_decima_timed {
+  double duration;          /* simulated time per call, ms */
+  double* clock;            /* [num_envs][2]: the time elapsed in this call (the caller zeroes it before a call; the
+                               call's final elapsed time afterwards), the wall time before the decision in flight */
+  const uint64_t* seeds;    /* [num_envs][cap_resets]: the reset schedule's seeds ... */
+  const double* limits;     /* [num_envs][cap_resets]: ... and time limits (+inf = none) */
+  int32_t* sched;           /* [num_envs][2]: slots consumed (the caller zeroes it when it fills the schedule); [1] = 1
+                               when the env stopped because its episode ended with no slot left (refill the schedule,
+                               clear both words, launch again: the env resets first and goes on) */
+  int32_t* reset_steps;     /* [num_envs][cap_resets]: per consumed slot, the index (the env's sample cursor - 1) of the
+                               sample whose step ended the episode (rollout_worker.py RolloutBuffer.add_reset) */
+  double* ep_arrival;       /* [num_envs][cap_resets][job_cap]: per consumed slot, the ended episode's job table as */
+  double* ep_completed;     /* ssim_job_times gives it, copied out before the reset wipes it */
+  int32_t* ep_state;
+  int32_t cap_resets;       /* slots per env, > 0 */
+  int32_t pad;
+} ssim_decima_timed;
+
+/* ssim_decima_rollout's arguments plus `timed`. Differences: the sample arena is required; a sample's wall_before holds
+ * the call's elapsed time before the decision; the sampling stream is (seed, env, counter + the env's sample cursor),
+ * whatever the episode (the lockstep collector's k-th decision of a call); flags: only 0 or SSIM_ROLLOUT_TEST_REJECT
+ * (SSIM_ROLLOUT_PREEMPT, SSIM_ROLLOUT_AUTORESET, SSIM_ROLLOUT_WARMUP, a decision budget or time_limits: SSIM_E_ARG;
+ * the limits come from the schedule). An env stops when its elapsed time reaches the duration, when a region of the
+ * arena is full (cursor[4], as ssim_decima_rollout), when its schedule is used up (sched[1]), after max_steps
+ * decisions of this launch, or when it is frozen. Needs job_arrival_gap in the config. */
+int ssim_decima_rollout_timed(ssim_handle* h, const float* params, int32_t num_params, float num_tasks_scale,
+                              float work_scale, uint64_t seed, uint64_t counter, int32_t max_steps,
+                              int64_t total_decisions, int32_t flags, const double* time_limits, void* workspace,
+                              int64_t workspace_bytes, const ssim_decima_samples* samples,
+                              const ssim_decima_timed* timed, int32_t* action_log, void* stream);
+
 const char* ssim_last_error(void);
 
 /* Test hook, not part of the drop-in surface: a trace of CPython-set operations (add / remove / idle order) on one
