@@ -182,6 +182,16 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, 64), amdgpu_waves_per_e
   rollout_body<kRes, kN, kJ, kS, HeuristicPolicy>(P, state, obs, HeuristicPolicy{kind, seed}, num_steps, flags, limits,
                                                   reset, action_log, prof_out, budget, env_steps);
 }
+// The rollout of the priority kinds (SSIM_POLICY_SJF / _SJF_CP; rollout.h PrioPolicy): the same loop under a second
+// action driver and its own symbol, instantiated for the two run-time-shape engines only (k_prio_lds.hip,
+// k_prio_hbm.hip), so k_rollout's instantiations are compiled from exactly the code they had before these kinds existed.
+// `seed` is unused (the rule is deterministic). SSIM_ROLLOUT_WARMUP launches the same symbol.
+template <bool kRes>
+__global__ __attribute__((amdgpu_flat_work_group_size(1, 64), amdgpu_waves_per_eu(SSIM_ROLLOUT_WAVES(kRes)))) void k_rollout_prio(SSIM_ROLLOUT_ARGS) {
+  (void)seed;
+  rollout_body<kRes, 0, 0, 0, PrioPolicy>(P, state, obs, PrioPolicy{kind}, num_steps, flags, limits, reset, action_log,
+                                          prof_out, budget, env_steps);
+}
 
 // Test hook (ssim_debug_set_trace_ex, tests/test_gpu_sets.py): a trace of CPython-set operations on one pool (job 0's)
 // of env 0 through the set code of the engine instantiation `Sim<WV, kN, kJ, kS>` with residency kRes — the template
@@ -255,3 +265,6 @@ KernelSet kernels_hbm();       // k_hbm.hip: hot block in HBM, any shape
 KernelSet kernels_hbm_n100();  // k_hbm_n100.hip: hot block in HBM, 100 executors / 200 jobs (configs[3] shard)
 KernelSet kernels_hbm_n10();   // k_hbm_n10.hip: hot block in HBM, 10 executors / 50 jobs (configs[1] env, large batches)
 KernelSet kernels_hbm_n50();   // k_hbm_n50.hip: hot block in HBM, 50 executors / 200 jobs (decima_tpch.yaml env)
+// the priority kinds' rollout (k_rollout_prio), one per residency
+RolloutFn rollout_prio_lds();  // k_prio_lds.hip: LDS-resident, any shape
+RolloutFn rollout_prio_hbm();  // k_prio_hbm.hip: hot block in HBM, any shape

@@ -7,6 +7,13 @@
 //                 random_scheduler.py:16-32's rejection loop), find_stage, num_exec ~ U{1..committable};
 //                 the stream is a counter-based splitmix64 of (seed, env, counter), so a run is exactly
 //                 reproducible; parity tests record these actions and replay them on the CPU oracle.
+//   SJF / SJF-CP: shortest job first (prio_job): the job with a schedulable stage and the least remaining work
+//                 W(k) = sum over its rows of float64(remaining tasks) * float64(most recent duration), added in row
+//                 order; ties to the earlier job. SJF takes that job's find_stage and all committable executors;
+//                 SJF-CP takes its schedulable row with the longest critical path cp(r) = w(r) + max(0, max cp(child))
+//                 (prio_cp_stage; ties to the lowest row). Their own driver (prio_act / sim_policy_prio) and their own
+//                 rollout kernel (kernels.h k_rollout_prio): policy_act is inlined into every tuned k_rollout
+//                 instantiation and stays as it is. DESIGN.md "Priority schedulers".
 #pragma once
 #include <stdint.h>
 
@@ -98,6 +105,118 @@ __device__ __forceinline__ StepIn policy_act(int kind, uint64_t seed, uint64_t c
   return a;
 }
 
+// ---------------------------------------------------------------------------------- SJF / SJF-CP (priority kinds)
+__device__ __forceinline__ bool policy_is_prio(int kind) {
+  return kind == SSIM_POLICY_SJF || kind == SSIM_POLICY_SJF_CP;
+}
+constexpr int kPrioMaxStages = 64;  // SJF-CP: one lane (one bit of a child set) per row of the chosen job
+
+// k* of the priority kinds: the active job with a pick (pick(k) >= 0) and the smallest (work(k), k); -1 if no job
+// has a pick. One lane per job, 64 jobs per round; work(k) >= 0 (a sum of products of non-negative floats), which
+// is what the bit-pattern minimum of WaveHip::min_d needs. Wave-uniform result.
+template <class W, class Work, class Pick>
+__device__ __forceinline__ int prio_job(int nj, Work work, Pick pick) {
+  double bw = __builtin_inf();
+  int bk = -1;
+  for (int k0 = 0; k0 < nj; k0 += W::kWidth) {
+    const int k = k0 + W::lane();
+    const bool c = k < nj && pick(k) >= 0;
+    const double w = c ? work(k) : __builtin_inf();
+    if constexpr (W::kWidth == 64) {
+      const double m = W::template min_d<64>(w);
+      const uint64_t eq = W::ballot(c && w == m);
+      if (eq != 0 && (bk < 0 || m < bw)) {  // (strict: a tie stays with the earlier round's job)
+        bw = m;
+        bk = k0 + W::ffs(eq);
+      }
+    } else {
+      if (c && (bk < 0 || w < bw)) {
+        bw = w;
+        bk = k;
+      }
+    }
+  }
+  return bk;
+}
+
+// The SJF-CP stage of the chosen job: its n <= 64 rows one per lane; row(l, &w, &kids, &rank) gives row l's work,
+// the set of its children's row numbers (bit c = an edge l -> c) and its rank among the env's schedulable rows
+// (-1: not schedulable; a lane that stands for no row of the observation reports w = 0, no children, rank -1 and is
+// in no other row's child set). cp(l) = w(l) + max(0, max over children cp(c)): rounds of relaxation from cp = w
+// until no lane changes (at most the DAG's depth + 1; capped at n + 1 so a corrupt edge list cannot spin). Returns the
+// rank of the schedulable row with the largest cp (lowest row on ties), -1 if none. Wave-uniform control flow.
+template <class W, class Row>
+__device__ __forceinline__ int prio_cp_stage(int n, Row row) {
+  if constexpr (W::kWidth == 64) {
+    const int l = W::lane();
+    double w = 0.0;
+    uint64_t kids = 0;
+    int rank = -1;
+    if (l < n) row(l, &w, &kids, &rank);
+    uint64_t all = 0;  // every row that is some row's child
+    for (uint64_t m = W::ballot(kids != 0); m != 0; m &= m - 1) {
+      const int b = W::ffs(m);
+      all |= (uint64_t)(uint32_t)W::bcast_i((int)(uint32_t)kids, b) |
+             ((uint64_t)(uint32_t)W::bcast_i((int)(uint32_t)(kids >> 32), b) << 32);
+    }
+    double cp = w;
+    for (int round = 0; round <= n; ++round) {
+      double best = 0.0;
+      for (uint64_t m = all; m != 0; m &= m - 1) {
+        const int b = W::ffs(m);
+        const double v = W::bcast_d(cp, b);
+        if (((kids >> b) & 1ull) != 0 && v > best) best = v;
+      }
+      const double next = w + best;
+      const bool moved = next != cp;
+      cp = next;
+      if (W::ballot(moved) == 0) break;
+    }
+    uint64_t m = W::ballot(rank >= 0);
+    if (m == 0) return -1;
+    int at = W::ffs(m);
+    double top = W::bcast_d(cp, at);
+    for (m &= m - 1; m != 0; m &= m - 1) {
+      const int b = W::ffs(m);
+      const double v = W::bcast_d(cp, b);
+      if (v > top) {
+        top = v;
+        at = b;
+      }
+    }
+    return W::bcast_i(rank, at);
+  } else {
+    double w[kPrioMaxStages], cp[kPrioMaxStages];
+    uint64_t kids[kPrioMaxStages];
+    int rank[kPrioMaxStages];
+    for (int l = 0; l < n; ++l) {
+      w[l] = 0.0;
+      kids[l] = 0;
+      rank[l] = -1;
+      row(l, &w[l], &kids[l], &rank[l]);
+      cp[l] = w[l];
+    }
+    for (int round = 0; round <= n; ++round) {
+      bool moved = false;
+      for (int l = 0; l < n; ++l) {
+        double best = 0.0;
+        for (uint64_t m = kids[l]; m != 0; m &= m - 1) {
+          const double v = cp[__builtin_ctzll(m)];
+          if (v > best) best = v;
+        }
+        const double next = w[l] + best;
+        moved = moved || next != cp[l];
+        cp[l] = next;
+      }
+      if (!moved) break;
+    }
+    int at = -1;
+    for (int l = 0; l < n; ++l)
+      if (rank[l] >= 0 && (at < 0 || cp[l] > cp[at])) at = l;
+    return at < 0 ? -1 : rank[at];
+  }
+}
+
 template <class W>
 struct PolicyView {
   const ssim_layout& L;
@@ -133,7 +252,66 @@ struct PolicyView {
     return fallback;
   }
 
+  __device__ __forceinline__ const float* nodes() const {
+    return reinterpret_cast<const float*>(obs + L.ob_nodes) + (int64_t)eid * L.stage_cap * 3;
+  }
+  __device__ __forceinline__ const int64_t* links() const {
+    return reinterpret_cast<const int64_t*>(obs + L.ob_edge_links) + (int64_t)eid * L.edge_cap * 2;
+  }
+
+  // SJF / SJF-CP on the observation (the rule at the top of this file, the specification's own arrays)
+  __device__ __forceinline__ StepIn prio_act(int kind) const {
+    const int32_t* c = counts();
+    const int32_t* p = ptr();
+    const float* nd = nodes();
+    const int nj = W::uni(c[SSIM_OC_NUM_JOBS]), comm = W::uni(c[SSIM_OC_COMMITTABLE]);
+    StepIn a;
+    a.stage_idx = -1;
+    a.num_exec = comm > 0 ? comm : 1;
+    const int ks = prio_job<W>(
+        nj,
+        [&](int k) {
+          double sum = 0.0;
+          for (int r = p[k]; r < p[k + 1]; ++r) sum += (double)nd[3 * r] * (double)nd[3 * r + 1];
+          return sum;
+        },
+        [&](int k) { return find_stage(k); });
+    if (ks < 0) return a;
+    a.num_exec = comm;
+    if (kind == SSIM_POLICY_SJF) {
+      a.stage_idx = W::uni(find_stage(ks));
+      return a;
+    }
+    const int lo = W::uni(p[ks]), hi = W::uni(p[ks + 1]);
+    if (hi - lo > kPrioMaxStages) return a;  // (ssim_policy refuses the config: max_stages > 64)
+    // the job's edges: the list is in node order, so they are the entries [e0, e1) with e0 = #(u < lo), e1 = #(u < hi)
+    const int64_t* ln = links();
+    int ne = W::uni(c[SSIM_OC_NUM_EDGES]);
+    ne = ne < L.edge_cap ? ne : L.edge_cap;
+    int e0 = 0, e1 = 0;
+    for (int i0 = 0; i0 < ne; i0 += W::kWidth) {
+      const int i = i0 + W::lane();
+      const int64_t u = i < ne ? ln[2 * i] : (int64_t)hi;
+      e0 += W::popc(W::ballot(u < lo));
+      e1 += W::popc(W::ballot(u < hi));
+    }
+    const int32_t* sr = srank();
+    a.stage_idx = prio_cp_stage<W>(hi - lo, [&](int l, double* w, uint64_t* kids, int* rank) {
+      const int r = lo + l;
+      *w = (double)nd[3 * r] * (double)nd[3 * r + 1];
+      *rank = sr[r];
+      uint64_t m = 0;
+      for (int e = e0; e < e1; ++e) {
+        const int64_t v = ln[2 * e + 1] - lo;
+        if (ln[2 * e] == r && v >= 0 && v < hi - lo) m |= 1ull << v;
+      }
+      *kids = m;
+    });
+    return a;
+  }
+
   __device__ __forceinline__ StepIn act(int kind, uint64_t seed, uint64_t counter) const {
+    if (policy_is_prio(kind)) return prio_act(kind);
     const int32_t* c = counts();
     const int32_t* su = sup();
     return policy_act<W>(kind, seed, counter, eid, L.num_executors, c[SSIM_OC_NUM_JOBS], c[SSIM_OC_COMMITTABLE],
@@ -143,9 +321,10 @@ struct PolicyView {
 };
 
 // The fused rollout's policy input: the header (loaded) and the picks of the env's last observation
-// (Sim::observe), read from the hot block instead of the obs arena the same wave just wrote.
+// (Sim::observe), read from the hot block instead of the obs arena the same wave just wrote. Fair / FIFO / random only
+// (HeuristicPolicy, the tuned k_rollout instantiations).
 template <class SimT>
-__device__ __forceinline__ StepIn sim_policy(SimT& s, int kind, uint64_t seed) {
+__device__ __forceinline__ StepIn sim_policy_legacy(SimT& s, int kind, uint64_t seed) {
   using W = typename SimT::WT;
   const int16_t* aj = s.template H<int16_t>(s.O.active_jobs);
   const uint64_t counter = (uint64_t)s.h.decisions + ((uint64_t)s.h.episode << 32);
@@ -156,6 +335,87 @@ __device__ __forceinline__ StepIn sim_policy(SimT& s, int kind, uint64_t seed) {
         return key == 0x7FFFFFFF ? -1 : (key & 0xFFFF);
       },
       [&](int k) { return (int)s.job(aj[k]).supply; });
+}
+
+// SJF / SJF-CP from the hot block: PolicyView::prio_act's rule on the stage records. A job's rows are its stages
+// that are not completed, in stage order (the active-stage list keeps node order), so its work is summed over all its
+// stage records (a completed stage has no remaining task: it adds +0.0, which changes no sum) and the CP lanes are its
+// local stage ids, a completed stage standing for no row. Children come from the dataset's topology (the bit sets of
+// templates of <= 32 stages, else the child lists) with observe()'s liveness test; the schedulable rows and their ranks
+// from the schedulable list observe() wrote (ascending stage index: one job's entries are contiguous).
+template <class SimT>
+__device__ __forceinline__ StepIn sim_policy_prio(SimT& s, int kind) {
+  using W = typename SimT::WT;
+  const int16_t* aj = s.template H<int16_t>(s.O.active_jobs);
+  const double* recent = s.recent();
+  const int comm = s.committable();
+  StepIn a;
+  a.stage_idx = -1;
+  a.num_exec = comm > 0 ? comm : 1;
+  const auto pick = [&](int k) {
+    const int key = s.job(aj[k]).pick;
+    return key == 0x7FFFFFFF ? -1 : (key & 0xFFFF);
+  };
+  const auto work = [&](int g) {
+    const StageRec sr = s.stage(g);
+    return (double)(float)sr.rem * (double)(float)recent[g];
+  };
+  const int ks = prio_job<W>(
+      s.h.n_active_jobs,
+      [&](int k) {
+        const JobRec jr = s.job(aj[k]);
+        double sum = 0.0;
+        for (int g = jr.base; g < jr.base + jr.nst; ++g) sum += work(g);
+        return sum;
+      },
+      pick);
+  if (ks < 0) return a;
+  a.num_exec = comm;
+  if (kind == SSIM_POLICY_SJF) {
+    a.stage_idx = W::uni(pick(ks));
+    return a;
+  }
+  const int j = W::uni(aj[ks]);
+  const int base = s.job_base(j), nst = s.job_nst(j);
+  if (nst > kPrioMaxStages) return a;  // (the rollout entry points refuse the config: max_stages > 64)
+  const typename SimT::TopoView tv = s.topo_view();
+  // the job's schedulable stages as a set of local ids, and the rank of the first of them
+  const int16_t* sched = s.template H<int16_t>(s.O.sched_list);
+  const int nsched = s.h.n_sched;
+  uint64_t smask = 0;
+  int first = -1;
+  for (int r0 = 0; r0 < nsched; r0 += W::kWidth) {
+    const int r = r0 + W::lane();
+    const int g = r < nsched ? (int)sched[r] : -1;
+    uint64_t m = W::ballot(g >= base && g < base + nst);
+    if (m != 0 && first < 0) first = r0 + W::ffs(m);
+    for (; m != 0; m &= m - 1) smask |= 1ull << (W::bcast_i(g, W::ffs(m)) - base);
+  }
+  a.stage_idx = prio_cp_stage<W>(nst, [&](int l, double* w, uint64_t* kids, int* rank) {
+    const StageRec sr = s.stage(base + l);
+    if (sr.rem == 0 && sr.exe == 0) return;  // completed: not a row of the observation
+    *w = (double)(float)sr.rem * (double)(float)recent[base + l];
+    if ((smask >> l) & 1ull) *rank = first + __builtin_popcountll(smask & ((1ull << l) - 1ull));
+    uint64_t m = 0;
+    const auto add_child = [&](int b) {
+      if (b < 0 || b >= nst) return;
+      const StageRec c = s.stage(base + b);
+      if (!(c.rem == 0 && c.exe == 0)) m |= 1ull << b;
+    };
+    if (tv.bits) {
+      for (uint32_t cm = (uint32_t)(ldg(tv.ts_topo, sr.ts) >> 32); cm != 0; cm &= cm - 1) add_child(__builtin_ctz(cm));
+    } else {
+      for (int k = ldg(tv.child_base, sr.ts); k < ldg(tv.child_base, sr.ts + 1); ++k) add_child(ldg(tv.children, k));
+    }
+    *kids = m;
+  });
+  return a;
+}
+
+// Any kind, from the hot block (the host build's rollout loop; the device kernels call the driver of their family).
+template <class SimT>
+__device__ __forceinline__ StepIn sim_policy(SimT& s, int kind, uint64_t seed) {
+  return policy_is_prio(kind) ? sim_policy_prio(s, kind) : sim_policy_legacy(s, kind, seed);
 }
 
 }  // namespace ssim

@@ -31,7 +31,27 @@ struct HeuristicPolicy {  // fair / FIFO / random (policy.h)
   }
   template <class S>
   __device__ __forceinline__ bool act(S& s, int /*k*/, StepIn* a) const {
-    *a = sim_policy(s, kind, seed);
+    *a = sim_policy_legacy(s, kind, seed);
+    return true;
+  }
+  template <class S>
+  __device__ __forceinline__ void done(S&) const {}
+  template <class S>
+  __device__ __forceinline__ void rejected(S&) const {}
+};
+
+// SJF / SJF-CP (policy.h sim_policy_prio): the action driver of k_rollout_prio (kernels.h), apart from HeuristicPolicy
+// so the tuned k_rollout instantiations carry none of its code.
+struct PrioPolicy {
+  static constexpr bool kTimedMode = false;
+  int kind;
+  template <class S>
+  __device__ __forceinline__ bool can_act(const S&) const {
+    return true;
+  }
+  template <class S>
+  __device__ __forceinline__ bool act(S& s, int /*k*/, StepIn* a) const {
+    *a = sim_policy_prio(s, kind);
     return true;
   }
   template <class S>

@@ -5,8 +5,9 @@
 // temporary CPython-set tables, commitment plan) lives in LDS. Kernels:
 //   k_reset   : env init from a host-sampled job sequence + _load_initial_jobs + first observation
 //   k_step    : one env.step per env from device action arrays (obs written to the obs arena)
-//   k_policy  : device action driver (fair / FIFO / random) reading the obs arena
-//   k_rollout : `num_steps` x (policy -> step) fused into one launch (no host round trips)
+//   k_policy  : device action driver (fair / FIFO / random / SJF / SJF-CP) reading the obs arena
+//   k_rollout : `num_steps` x (policy -> step) fused into one launch (no host round trips); k_rollout_prio for the
+//               SJF / SJF-CP kinds
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
 #include <stdlib.h>
@@ -145,6 +146,13 @@ static DecimaRolloutSet pick_decima(const Params& p) {
                                                                                           : decima_rollout_lds())
          : !decima_shape(p) || generic_forced()   ? decima_rollout_hbm()
                                                   : decima_rollout_hbm50();
+}
+// The priority kinds (SJF / SJF-CP) run k_rollout_prio, which exists for the two run-time-shape engines only.
+static bool prio_kind(int32_t kind) { return kind == SSIM_POLICY_SJF || kind == SSIM_POLICY_SJF_CP; }
+static RolloutFn pick_prio(const Params& p) { return p.O.lds_resident ? rollout_prio_lds() : rollout_prio_hbm(); }
+static const char* prio_name(const Params& p) { return p.O.lds_resident ? "prio_lds" : "prio_hbm"; }
+static bool known_kind(int32_t kind) {
+  return kind == SSIM_POLICY_FAIR || kind == SSIM_POLICY_FIFO || kind == SSIM_POLICY_RANDOM || prio_kind(kind);
 }
 static StepFn pick_step(const Params& p) { return pick_kernels(p).step; }
 static RolloutFn pick_rollout(const Params& p, bool warmup = false) {
@@ -334,8 +342,10 @@ extern "C" int ssim_step(ssim_handle* h, const int32_t* stage_idx, const int32_t
 extern "C" int ssim_policy(ssim_handle* h, int32_t kind, uint64_t seed, uint64_t counter, int32_t* stage_idx,
                            int32_t* num_exec, void* stream) {
   if (h == nullptr || stage_idx == nullptr || num_exec == nullptr) return set_err(SSIM_E_ARG, "ssim_policy: null");
-  if (kind != SSIM_POLICY_FAIR && kind != SSIM_POLICY_FIFO && kind != SSIM_POLICY_RANDOM)
-    return set_err(SSIM_E_ARG, "ssim_policy: unknown policy %d", kind);
+  if (!known_kind(kind)) return set_err(SSIM_E_ARG, "ssim_policy: unknown policy %d", kind);
+  if (kind == SSIM_POLICY_SJF_CP && h->params.C.max_stages > kPrioMaxStages)
+    return set_err(SSIM_E_ARG, "ssim_policy: SSIM_POLICY_SJF_CP supports at most %d stages per job (max_stages %d)",
+                   kPrioMaxStages, h->params.C.max_stages);
   const ssim_layout& L = h->params.L;
   hipLaunchKernelGGL(k_policy, dim3(L.num_envs), dim3(64), 0, (hipStream_t)stream, dparams(h), h->obs, kind,
                      seed, counter, stage_idx, num_exec);
@@ -346,8 +356,10 @@ static int rollout_launch(ssim_handle* h, int32_t kind, uint64_t seed, int32_t n
                           int32_t flags, const double* time_limits, int32_t* action_log, void* stream,
                           const int32_t* env_steps = nullptr) {
   if (h == nullptr || num_steps < 0 || budget < 0) return set_err(SSIM_E_ARG, "ssim_rollout: bad argument");
-  if (kind != SSIM_POLICY_FAIR && kind != SSIM_POLICY_FIFO && kind != SSIM_POLICY_RANDOM)
-    return set_err(SSIM_E_ARG, "ssim_rollout: unknown policy %d", kind);
+  if (!known_kind(kind)) return set_err(SSIM_E_ARG, "ssim_rollout: unknown policy %d", kind);
+  if (kind == SSIM_POLICY_SJF_CP && h->params.C.max_stages > kPrioMaxStages)
+    return set_err(SSIM_E_ARG, "ssim_rollout: SSIM_POLICY_SJF_CP supports at most %d stages per job (max_stages %d)",
+                   kPrioMaxStages, h->params.C.max_stages);
   if ((flags & ~(SSIM_ROLLOUT_AUTORESET | SSIM_ROLLOUT_PREEMPT | SSIM_ROLLOUT_WARMUP)) != 0)
     return set_err(SSIM_E_ARG, "ssim_rollout_ex: unknown flags 0x%x", flags);
   if ((flags & SSIM_ROLLOUT_PREEMPT) && budget <= 0)
@@ -356,7 +368,8 @@ static int rollout_launch(ssim_handle* h, int32_t kind, uint64_t seed, int32_t n
     return set_err(SSIM_E_ARG, "ssim_rollout_ex: auto-reset needs job_arrival_gap in the config");
   const ssim_layout& L = h->params.L;
   const KernelSet ks = pick_kernels(h->params);
-  const RolloutFn fn = (flags & SSIM_ROLLOUT_WARMUP) ? ks.rollout_warmup : ks.rollout;
+  const RolloutFn fn = prio_kind(kind) ? pick_prio(h->params)  // (one symbol: warm-up launches included)
+                                       : (flags & SSIM_ROLLOUT_WARMUP) ? ks.rollout_warmup : ks.rollout;
   const int64_t lds = h->params.O.lds_bytes;
   const int rc = lds_opt_in((const void*)fn, lds);
   if (rc != SSIM_OK) return rc;
@@ -481,6 +494,7 @@ static const char* debug_variant(const ssim_handle* h, int32_t variant, SetTrace
 }
 
 extern "C" const char* ssim_debug_kernel_name(const ssim_handle* h, int32_t variant) {
+  if (h != nullptr && variant == SSIM_DEBUG_PRIO) return prio_name(h->params);  // (a name only: no set KAT of its own)
   SetTraceFn fn;
   const char* n = h != nullptr ? debug_variant(h, variant, &fn) : nullptr;
   return n != nullptr ? n : "";

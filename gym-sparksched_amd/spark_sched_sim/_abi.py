@@ -13,6 +13,7 @@ SSIM_ROLLOUT_PREEMPT = 0x2
 SSIM_ROLLOUT_WARMUP = 0x4
 SSIM_ROLLOUT_TEST_REJECT = 0x8  # ssim_decima_rollout test hook
 SSIM_DEBUG_ENGINE, SSIM_DEBUG_DECIMA, SSIM_DEBUG_KAT_BAD = 0, 1, 2  # ssim_debug_set_trace_ex variants
+SSIM_DEBUG_PRIO = 3  # ssim_debug_kernel_name only: the SJF / SJF-CP rollout unit of a handle
 SSIM_ACT_LEAKY_RELU, SSIM_ACT_TANH = 0, 1  # ssim_mlp3_* activations
 SSIM_ERR_SPACE = 0x1
 SSIM_ERR_KEY = 0x2
@@ -27,6 +28,11 @@ SSIM_ERR_STICKY = 0xF0
 SSIM_POLICY_FAIR = 1
 SSIM_POLICY_FIFO = 2
 SSIM_POLICY_RANDOM = 3
+SSIM_POLICY_SJF = 4     # shortest job first (least remaining work), the job's find_stage stage
+SSIM_POLICY_SJF_CP = 5  # shortest job first, its schedulable stage with the longest critical path
+# scheduler name -> device policy kind (examples.py --sched, evaluate.evaluate_policy)
+POLICY_KINDS = {"fair": SSIM_POLICY_FAIR, "fifo": SSIM_POLICY_FIFO, "random": SSIM_POLICY_RANDOM,
+                "sjf": SSIM_POLICY_SJF, "sjf-cp": SSIM_POLICY_SJF_CP}
 
 # indices into the per-env int32 counts block
 OC_NUM_NODES, OC_NUM_EDGES, OC_NUM_JOBS, OC_COMMITTABLE, OC_SOURCE_JOB_IDX, OC_NUM_SCHEDULABLE = range(6)

@@ -5,6 +5,7 @@ a gfx950 kernel launch through the C ABI) driven by a host scheduler's `schedule
 average job duration in seconds (`metrics.avg_job_duration(env) * 1e-3`).
 
     python -m spark_sched_sim.examples --sched fair      # examples.py --sched fair (BASELINE configs[0])
+    python -m spark_sched_sim.examples --sched sjf-cp    # shortest job first, critical-path stage choice
 """
 
 from __future__ import annotations
@@ -14,7 +15,7 @@ from pprint import pprint
 
 from . import metrics
 from .env import SparkSchedSimEnv
-from .schedulers import RandomScheduler, RoundRobinScheduler
+from .schedulers import POLICY_KINDS, host_scheduler
 
 ENV_CFG = {  # examples.py:15-23, without the pygame renderer
     "num_executors": 10,
@@ -42,13 +43,10 @@ def run_episode(env_cfg: dict, scheduler, seed: int = 1234, **env_kwargs) -> flo
 
 def main(argv=None) -> None:
     parser = ArgumentParser(description=__doc__, formatter_class=ArgumentDefaultsHelpFormatter)
-    parser.add_argument("--sched", choices=["fair", "fifo", "random"], required=True)
+    parser.add_argument("--sched", choices=list(POLICY_KINDS), required=True)
     parser.add_argument("--seed", type=int, default=1234)
     args = parser.parse_args(argv)
-    n = ENV_CFG["num_executors"]
-    scheduler = {"fair": lambda: RoundRobinScheduler(n, dynamic_partition=True),
-                 "fifo": lambda: RoundRobinScheduler(n, dynamic_partition=False),
-                 "random": lambda: RandomScheduler(42)}[args.sched]()
+    scheduler = host_scheduler(args.sched, ENV_CFG["num_executors"], seed=42)
     print(f"Example: {scheduler.name} Scheduler")
     print("Env settings:")
     pprint(ENV_CFG)

@@ -1,13 +1,19 @@
 """Scheduler plugins (reference `schedulers/__init__.py`): host heuristics over the facade's obs dicts, the
 batched Decima GNN over device observations, and `make_scheduler` by class name. The batched device action
-drivers (fair / FIFO / random) used inside the rollout kernels are in csrc/policy.h."""
+drivers (fair / FIFO / random / SJF / SJF-CP) used inside the rollout kernels are in csrc/policy.h; `POLICY_KINDS`
+maps their names to the device policy kinds."""
 
 __all__ = ["Scheduler", "DecimaScheduler", "RandomScheduler", "RoundRobinScheduler", "make_scheduler",
-           "preprocess_obs", "find_stage"]
+           "preprocess_obs", "find_stage", "ShortestJobFirstScheduler", "POLICY_KINDS", "host_scheduler"]
+
+# the classes make_scheduler instantiates by name
+SCHEDULER_CLASSES = ("DecimaScheduler", "RandomScheduler", "RoundRobinScheduler", "ShortestJobFirstScheduler")
 
 from copy import deepcopy
 
-from .heuristics import RandomScheduler, RoundRobinScheduler, Scheduler, find_stage, preprocess_obs
+from .._abi import POLICY_KINDS
+from .heuristics import (RandomScheduler, RoundRobinScheduler, Scheduler, ShortestJobFirstScheduler, find_stage,
+                         preprocess_obs)
 
 
 def __getattr__(name):  # torch is imported only when the GNN is asked for
@@ -22,6 +28,18 @@ def make_scheduler(agent_cfg: dict):
     """Instantiate `agent_cfg["agent_cls"]` with the whole config as keyword arguments
     (schedulers/__init__.py:16-20)."""
     cls = agent_cfg["agent_cls"]
-    if cls not in __all__[:4]:
+    if cls not in SCHEDULER_CLASSES:
         raise AssertionError(f"'{cls}' is not a valid scheduler.")
     return (globals().get(cls) or __getattr__(cls))(**deepcopy(agent_cfg))
+
+
+def host_scheduler(name: str, num_executors: int, seed: int = 42):
+    """The host scheduler whose device equivalent is policy kind `POLICY_KINDS[name]`: fair, fifo, random, sjf,
+    sjf-cp."""
+    if name not in POLICY_KINDS:
+        raise ValueError(f"unknown scheduler '{name}' (one of {sorted(POLICY_KINDS)})")
+    if name == "random":
+        return RandomScheduler(seed=seed)
+    if name in ("sjf", "sjf-cp"):
+        return ShortestJobFirstScheduler(num_executors, critical_path=name == "sjf-cp")
+    return RoundRobinScheduler(num_executors, dynamic_partition=name == "fair")

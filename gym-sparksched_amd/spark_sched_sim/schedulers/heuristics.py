@@ -113,3 +113,85 @@ class RandomScheduler(Scheduler):
             candidates.remove(j)
         num_exec = self.np_random.randint(1, obs["num_committable_execs"] + 1)
         return {"stage_idx": k, "num_exec": num_exec}, {}
+
+
+class ShortestJobFirstScheduler(Scheduler):
+    """Shortest job first, optionally with critical-path stage choice (SJF / SJF-CP); the specification the device
+    kinds `SSIM_POLICY_SJF` / `SSIM_POLICY_SJF_CP` (csrc/policy.h) follow action for action.
+
+    w(r) = float64(nodes[r, 0]) * float64(nodes[r, 1]) (remaining tasks x most recent task duration; exact in
+    float64). W(k) = the float64 sum of w over job k's rows, added one at a time in row order from 0.0. Among the
+    jobs with a schedulable stage (`find_stage(obs, k) != -1`) the one with the smallest (W(k), k) is served with
+    every committable executor: SJF takes its `find_stage` stage; SJF-CP its schedulable row with the largest
+    cp(r) = w(r) + max(0.0, max over edges (r, c) of cp(c)), the lowest row on ties. With no candidate the action is
+    the other heuristics' "nothing to schedule": stage_idx -1. There is no source-job preference and no per-job cap.
+    A pure function of the observation."""
+
+    def __init__(self, num_executors: int, critical_path: bool = False, **kwargs):
+        self.name = "SJF-CP" if critical_path else "SJF"
+        self.num_executors = num_executors
+        self.critical_path = critical_path
+        self.env_wrapper_cls = None
+
+    @staticmethod
+    def row_work(obs: dict) -> np.ndarray:
+        nodes = np.asarray(obs["dag_batch"].nodes)
+        return nodes[:, 0].astype(np.float64) * nodes[:, 1].astype(np.float64)
+
+    @staticmethod
+    def job_work(obs: dict, w: np.ndarray, k: int) -> float:
+        total = 0.0
+        for r in range(int(obs["dag_ptr"][k]), int(obs["dag_ptr"][k + 1])):
+            total += float(w[r])
+        return total
+
+    def choose_job(self, obs: dict, w: np.ndarray) -> int:
+        """k*: the candidate with the smallest (W, k), -1 if no job has a schedulable stage (after preprocess_obs)."""
+        best, best_w = -1, 0.0
+        for k in range(len(obs["dag_ptr"]) - 1):
+            if find_stage(obs, k) == -1:
+                continue
+            wk = self.job_work(obs, w, k)
+            if best < 0 or wk < best_w:
+                best, best_w = k, wk
+        return best
+
+    @staticmethod
+    def critical_paths(obs: dict, w: np.ndarray, lo: int, hi: int) -> dict:
+        """cp(r) of the rows lo <= r < hi of one job (the edges of a job stay within its rows)."""
+        links = np.asarray(obs["dag_batch"].edge_links).reshape(-1, 2)
+        kids: dict[int, list] = {r: [] for r in range(lo, hi)}
+        for u, v in links.tolist():
+            if lo <= u < hi:
+                kids[int(u)].append(int(v))
+        cp: dict[int, float] = {}
+
+        def visit(r):
+            if r not in cp:
+                tail = 0.0
+                for c in kids[r]:
+                    tail = max(tail, visit(c))
+                cp[r] = float(w[r]) + tail
+            return cp[r]
+
+        for r in range(lo, hi):
+            visit(r)
+        return cp
+
+    def schedule(self, obs: dict) -> tuple[dict, dict]:
+        preprocess_obs(obs)
+        committable = obs["num_committable_execs"]
+        w = self.row_work(obs)
+        k = self.choose_job(obs, w)
+        if k < 0:
+            return {"stage_idx": -1, "num_exec": committable}, {}
+        if not self.critical_path:
+            return {"stage_idx": find_stage(obs, k), "num_exec": committable}, {}
+        lo, hi = int(obs["dag_ptr"][k]), int(obs["dag_ptr"][k + 1])
+        cp = self.critical_paths(obs, w, lo, hi)
+        sched = obs["schedulable_stages"]
+        best = -1
+        for r in range(lo, hi):
+            if r in sched and (best < 0 or cp[r] > cp[best]):
+                best = r
+        return {"stage_idx": sched[best], "num_exec": committable}, {}

@@ -100,11 +100,15 @@ class SparkSchedSimVecEnv:
         return self.obs, self.engine.views["reward"], term, trunc, self._info()
 
     def policy(self, kind: int = _abi.SSIM_POLICY_FAIR, seed: int = 0, counter: int = 0):
-        """On-device action driver (fair / FIFO / random); returns (stage_idx, num_exec) tensors."""
+        """On-device action driver: `kind` is one of _abi.SSIM_POLICY_FAIR / _FIFO / _RANDOM / _SJF / _SJF_CP
+        (_abi.POLICY_KINDS by name; seed / counter feed the random kind only, SJF-CP needs max_stages <= 64);
+        returns (stage_idx, num_exec) tensors."""
         return self.engine.policy(kind, seed, counter)
 
     def rollout(self, kind: int, seed: int, num_steps: int, action_log=None):
-        """`num_steps` device-policy decisions per env fused into one launch."""
+        """`num_steps` device-policy decisions per env fused into one launch, for any policy kind of `policy`. The
+        SJF / SJF-CP kinds run the run-time-shape rollout kernel of the layout's residency
+        (evaluate.evaluate_policy runs whole episodes this way)."""
         self.engine.rollout(kind, seed, num_steps, action_log)
 
     def decima_features(self, num_tasks_scale: float = 200.0, work_scale: float = 1e5) -> dict:

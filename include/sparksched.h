@@ -43,6 +43,14 @@ extern "C" {
 #define SSIM_POLICY_FAIR 1    /* RoundRobinScheduler(dynamic_partition=True), round_robin.py:14-49 */
 #define SSIM_POLICY_FIFO 2    /* RoundRobinScheduler(dynamic_partition=False) */
 #define SSIM_POLICY_RANDOM 3  /* uniform-random valid action from a counter-based device RNG */
+/* Shortest job first: among the active jobs that have a schedulable stage, the one with the least remaining work
+ * (float64 sum over its nodes, in node order, of remaining tasks x most recent task duration; ties to the earlier
+ * job); num_exec = all committable executors. SJF takes the job's find_stage stage; SJF_CP its schedulable stage with
+ * the longest critical path, cp(r) = work(r) + max(0, max over active children cp(c)) (ties to the lowest node), and
+ * needs max_stages <= 64 (SSIM_E_ARG otherwise). seed / counter are ignored. The fused rollouts run these kinds on the
+ * run-time-shape kernels of either residency (ssim_debug_kernel_name(h, SSIM_DEBUG_PRIO)). */
+#define SSIM_POLICY_SJF 4
+#define SSIM_POLICY_SJF_CP 5
 
 /* Env configuration (spark_sched_sim.py:37-52, tpch.py:19-49). */
 typedef struct ssim_config {
@@ -379,6 +387,7 @@ int ssim_debug_set_trace(ssim_handle* h, const int32_t* ops, int32_t n_ops, int3
 #define SSIM_DEBUG_ENGINE 0
 #define SSIM_DEBUG_DECIMA 1
 #define SSIM_DEBUG_KAT_BAD 2
+#define SSIM_DEBUG_PRIO 3 /* ssim_debug_kernel_name only: the unit an SJF / SJF-CP rollout on this handle launches */
 int ssim_debug_set_trace_ex(ssim_handle* h, const int32_t* ops, int32_t n_ops, int32_t width, int32_t* orders,
                             int32_t variant, void* stream);
 /* Name of the kernel translation unit a variant selects for this handle ("hbm_n100", "bench900", "dr_hbm50", ...; ""
