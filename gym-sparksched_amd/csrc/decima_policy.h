@@ -477,8 +477,9 @@ __device__ __forceinline__ float* dp_help_gs(DpHelp* hb, int N, int c) {
 }
 
 // The mailbox's tiles assigned to wave w: tile j (candidates in order, then rows) runs on wave first + j % (waves -
-// first); action k of candidate c: its score into sc[c][k], its Gumbel-perturbed score into gs[c][k].
-template <class WS>
+// first); action k of candidate c: its score into sc[c][k], its Gumbel-perturbed score into gs[c][k]
+// (kGreedy: no noise, the score itself).
+template <bool kGreedy = false, class WS>
 __device__ __forceinline__ void dp_exec_tiles(const WS& Wt, DpHelp* hb, int N, int w) {
   using W = WaveHip;
   const int nc = W::uni(hb->ncand), first = W::uni(hb->first);
@@ -496,18 +497,20 @@ __device__ __forceinline__ void dp_exec_tiles(const WS& Wt, DpHelp* hb, int N, i
       });
       if (k < cap && hl == 0) {
         dp_help_sc(hb, N, c)[k] = sc;
-        dp_help_gs(hb, N, c)[k] = sc + dp_gumbel(key ^ 0xE7037ED1A0B428DBULL, (uint64_t)k);
+        float noise = 0.0f;
+        if constexpr (!kGreedy) noise = dp_gumbel(key ^ 0xE7037ED1A0B428DBULL, (uint64_t)k);
+        dp_help_gs(hb, N, c)[k] = sc + noise;
       }
     }
   }
 }
 // The helper waves' loop (waves 1 .. kDpHelpWaves - 1 of a helped workgroup)
-template <class WS>
+template <bool kGreedy = false, class WS>
 __device__ __forceinline__ void dp_help_loop(const WS& Wt, DpHelp* hb, int N, int w) {
   for (;;) {
     __syncthreads();  // A: a decision's inputs published, or the exit
     if (WaveHip::uni(hb->cmd) != kDpHelpWork) return;
-    dp_exec_tiles(Wt, hb, N, w);
+    dp_exec_tiles<kGreedy>(Wt, hb, N, w);
     __syncthreads();  // B: scores written
   }
 }
@@ -550,8 +553,11 @@ __device__ __forceinline__ float dp_ld(const float* p) {
 // (k_decima_policy) or, with kGlobal, a per-env region of global memory (the persistent Decima rollout, whose
 // 16 waves per CU leave no LDS for a J=200 plan); the atomic accumulation phases then end with an agent-scope
 // fence (decima.h scratch_sync). `act` (optional) receives the action. kHelp: the exec scores run on the workgroup's
-// helper waves through the LDS mailbox `help` (dp_exec_tiles).
-template <bool kGlobal = false, bool kHelp = false, class WS>
+// helper waves through the LDS mailbox `help` (dp_exec_tiles). kGreedy: the arg-max action instead of a draw: the noise
+// term is 0 at every site that adds dp_gumbel (seed / counter unused), ties between bit-equal scores go to the lowest
+// schedulable node and the lowest k; scores, the log-softmax and lgprob (of the chosen pair) are as in the sampled
+// mode. It alters values only: the barriers, `publish` and the helpers' A / B pairs are those of the sampled mode.
+template <bool kGlobal = false, bool kHelp = false, bool kGreedy = false, class WS>
 __device__ __forceinline__ bool decima_policy_env(const Params* __restrict__ P, const uint8_t* __restrict__ obs,
                                          const float* __restrict__ feats, const int32_t* __restrict__ ccap,
                                          const uint32_t* __restrict__ emask, const int32_t* __restrict__ depth,
@@ -858,7 +864,9 @@ __device__ __forceinline__ bool decima_policy_env(const Params* __restrict__ P, 
       score[i] = sc;
       if (o.stage_scores) o.stage_scores[(int64_t)eid * S + i] = sc;
       mx = sc > mx ? sc : mx;
-      const float gs = sc + dp_gumbel(key, (uint64_t)i);
+      float noise = 0.0f;
+      if constexpr (!kGreedy) noise = dp_gumbel(key, (uint64_t)i);
+      const float gs = sc + noise;
       if (gs > best) {
         best = gs;
         pick = i;
@@ -923,7 +931,7 @@ __device__ __forceinline__ bool decima_policy_env(const Params* __restrict__ P, 
       const bool many = cap > 16;  // one tile: no helpers needed
       if (many) __syncthreads();  // A
       else W::sync();
-      dp_exec_tiles(Wt, help, N, 0);
+      dp_exec_tiles<kGreedy>(Wt, help, N, 0);
       if (many) __syncthreads();  // B
       else W::sync();
     }
@@ -959,7 +967,9 @@ __device__ __forceinline__ bool decima_policy_env(const Params* __restrict__ P, 
       escore[k] = sc;
       if (o.exec_scores) o.exec_scores[(int64_t)eid * N + k] = sc;
       emx = sc > emx ? sc : emx;
-      const float gs = sc + dp_gumbel(key ^ 0xE7037ED1A0B428DBULL, (uint64_t)k);
+      float noise = 0.0f;
+      if constexpr (!kGreedy) noise = dp_gumbel(key ^ 0xE7037ED1A0B428DBULL, (uint64_t)k);
+      const float gs = sc + noise;
       if (gs > ebest) {
         ebest = gs;
         epick = k;
@@ -978,7 +988,17 @@ __device__ __forceinline__ bool decima_policy_env(const Params* __restrict__ P, 
   int kx = 0;
   float sk = 0.0f;
   if (ew) {
-    const int l = W::ffs(ew);
+    int l = W::ffs(ew);
+    if constexpr (kGreedy) {  // lane rl holds k = rl, 16 + rl, ...: among the tied lanes, the one with the lowest k
+      int kmin = 0x7FFFFFFF;
+      for (uint64_t m = ew; m; m &= m - 1) {
+        const int cand = W::bcast_i(epick, W::ffs(m));
+        if (cand < kmin) {
+          kmin = cand;
+          l = W::ffs(m);
+        }
+      }
+    }
     kx = W::bcast_i(epick, l);
     sk = __builtin_bit_cast(float, W::bcast_i(__builtin_bit_cast(int, es_k), l));
   }

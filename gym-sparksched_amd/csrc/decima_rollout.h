@@ -78,7 +78,7 @@ struct DecimaRolloutArgs {
 // observation has at most `plan_cap` nodes (0: in the env's global workspace: feat_scratch / plan). (Inlined: as a
 // call, the calling convention saved every live register around it, 1.2 KB per lane of scratch.) kHelp: the exec
 // scores on the workgroup's helper waves, through the mailbox at LDS byte `help_lds` (decima_policy.h dp_exec_tiles).
-template <bool kHelp = false>
+template <bool kHelp = false, bool kGreedy = false>
 __device__ __forceinline__ DpAction decima_decide(
     const Params* P0, const uint8_t* obs0, const dp_f32x4* weights0, uint8_t* feat_scratch0, uint8_t* plan0,
     float* feats0, int32_t* ccap0, uint32_t* emask0, int32_t* depth0, float num_tasks_scale, float work_scale,
@@ -110,7 +110,7 @@ __device__ __forceinline__ DpAction decima_decide(
 #ifdef SSIM_PROFILE
     if (pprof != nullptr && W::lane() == 0) W::lds_add_u64(pprof - kPhDecParts + kPhDecFeat, W::clock() - tp);
 #endif
-    decima_policy_env<false, kHelp>(P, obs, feats, ccap, emask, depth, wts, plan_cap, seed, ctr, eid, pl, none, &act,
+    decima_policy_env<false, kHelp, kGreedy>(P, obs, feats, ccap, emask, depth, wts, plan_cap, seed, ctr, eid, pl, none, &act,
                                     pprof, kDpLdsDags, help);
   } else {  // the env's global workspace
     uint8_t* fs = (uint8_t*)(SSIM_GLOBAL uint8_t*)feat_scratch0;
@@ -119,7 +119,7 @@ __device__ __forceinline__ DpAction decima_decide(
 #ifdef SSIM_PROFILE
     if (pprof != nullptr && W::lane() == 0) W::lds_add_u64(pprof - kPhDecParts + kPhDecFeat, W::clock() - tp);
 #endif
-    decima_policy_env<true, kHelp>(P, obs, feats, ccap, emask, depth, wts, L.stage_cap, seed, ctr, eid, pg, none, &act,
+    decima_policy_env<true, kHelp, kGreedy>(P, obs, feats, ccap, emask, depth, wts, L.stage_cap, seed, ctr, eid, pg, none, &act,
                                    pprof, 0, help);
   }
   return act;
@@ -131,7 +131,7 @@ __device__ __forceinline__ DpAction decima_decide(
 struct DecimaTimedNone {};
 template <bool kTimed>
 using DecimaTimedArgs = std::conditional_t<kTimed, ssim_decima_timed, DecimaTimedNone>;
-template <bool kHelp = false, bool kTimed = false>
+template <bool kHelp = false, bool kTimed = false, bool kGreedy = false>
 struct DecimaPolicy {
   static constexpr bool kTimedMode = kTimed;
   const Params* P;
@@ -261,7 +261,7 @@ struct DecimaPolicy {
 #endif
     const bool lds_plan = n <= a.plan_cap && nj <= kDpLdsDags;
     SSIM_MARK("decima_policy_begin");
-    const DpAction act = decima_decide<kHelp>(P, obs, a.weights, wk + a.wl.feat_scratch, wk + a.wl.plan, feats, ccap, emask,
+    const DpAction act = decima_decide<kHelp, kGreedy>(P, obs, a.weights, wk + a.wl.feat_scratch, wk + a.wl.plan, feats, ccap, emask,
                                        depth, a.num_tasks_scale, a.work_scale, a.seed, ctr, eid,
                                        lds_plan ? a.plan_cap : 0,
                                        (uint32_t)(s.scr + a.plan_off - g_smem), pprof, (uint32_t)a.help_off);
@@ -380,7 +380,7 @@ struct DecimaPolicy {
 // kN / kJ: executor count and job cap as compile-time constants (0 = read from the layout), as kernels.h. kHelp: the
 // workgroup is kDpHelpWaves waves; wave 0 runs the env, the others its exec-score tiles (decima_policy.h), until wave 0
 // publishes kDpHelpExit at the end of its rollout (every path out of rollout_body comes back here).
-template <bool kRes, int kN, int kJ, bool kHelp, bool kTimed = false>
+template <bool kRes, int kN, int kJ, bool kHelp, bool kTimed = false, bool kGreedy = false>
 __device__ __forceinline__ void decima_rollout_body(const Params* __restrict__ P, uint8_t* state, uint8_t* obs,
                                                     DecimaRolloutArgs a, int num_steps, int flags,
                                                     const double* __restrict__ limits, uint8_t* reset,
@@ -391,14 +391,14 @@ __device__ __forceinline__ void decima_rollout_body(const Params* __restrict__ P
     const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     if (wv != 0) {
       const DpWGlobal wts{(const dp_f32x4*)(const SSIM_GLOBAL dp_f32x4*)a.weights};
-      dp_help_loop(wts, help, kN > 0 ? kN : P->L.num_executors, wv);
+      dp_help_loop<kGreedy>(wts, help, kN > 0 ? kN : P->L.num_executors, wv);
       return;
     }
   }
   a.autoreset = (flags & SSIM_ROLLOUT_AUTORESET) != 0;
   a.test_reject = (flags & SSIM_ROLLOUT_TEST_REJECT) != 0;
-  const DecimaPolicy<kHelp, kTimed> pol{P, obs, a, t};
-  rollout_body<kRes, kN, kJ, 0, DecimaPolicy<kHelp, kTimed>>(P, state, obs, pol, num_steps, flags, limits, reset,
+  const DecimaPolicy<kHelp, kTimed, kGreedy> pol{P, obs, a, t};
+  rollout_body<kRes, kN, kJ, 0, DecimaPolicy<kHelp, kTimed, kGreedy>>(P, state, obs, pol, num_steps, flags, limits, reset,
                                                              action_log, prof_out, budget, nullptr, !kRes,
                                                              SSIM_DR_EX_LDS != 0);
   if constexpr (kHelp) {
@@ -432,6 +432,15 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, SSIM_DR_THREADS(kHelp))
   decima_rollout_body<kRes, kN, kJ, kHelp, true>(P, state, obs, a, num_steps, flags, nullptr, reset, action_log, 0,
                                                  prof_out, t);
 }
+// greedy rollouts (ssim_decima_rollout with SSIM_ROLLOUT_GREEDY: the policy's arg-max action, decima_policy.h
+// kGreedy): their own kernels, in their own translation units (k_drg_*.hip), as the timed ones
+template <bool kRes, int kN = 0, int kJ = 0, bool kHelp = false>
+__global__ __attribute__((amdgpu_flat_work_group_size(1, SSIM_DR_THREADS(kHelp)), amdgpu_waves_per_eu(SSIM_DR_WAVES(kRes)))) void k_decima_rollout_greedy(
+    const Params* __restrict__ P, uint8_t* state, uint8_t* obs, DecimaRolloutArgs a, int num_steps, int flags,
+    const double* __restrict__ limits, uint8_t* reset, int32_t* action_log, int64_t budget, uint64_t* prof_out) {
+  decima_rollout_body<kRes, kN, kJ, kHelp, false, true>(P, state, obs, a, num_steps, flags, limits, reset, action_log,
+                                                        budget, prof_out);
+}
 
 using DecimaRolloutFn = void (*)(const Params*, uint8_t*, uint8_t*, DecimaRolloutArgs, int, int, const double*,
                                  uint8_t*, int32_t*, int64_t, uint64_t*);
@@ -448,6 +457,14 @@ DecimaTimedFn decima_timed_hbm();    // k_drt_hbm.hip
 DecimaTimedFn decima_timed_hbm50();  // k_drt_hbm50.hip
 DecimaTimedFn decima_timed_lds();    // k_drt_lds.hip
 DecimaTimedFn decima_timed_lds50();  // k_drt_lds50.hip
+struct DecimaGreedySet {
+  DecimaRolloutFn rollout;
+  const char* name;  // the translation unit (ssim_debug_kernel_name, SSIM_DEBUG_DECIMA_GREEDY)
+};
+DecimaGreedySet decima_greedy_hbm();    // k_drg_hbm.hip
+DecimaGreedySet decima_greedy_hbm50();  // k_drg_hbm50.hip
+DecimaGreedySet decima_greedy_lds();    // k_drg_lds.hip
+DecimaGreedySet decima_greedy_lds50();  // k_drg_lds50.hip
 DecimaRolloutSet decima_rollout_hbm();    // k_dr_hbm.hip
 DecimaRolloutSet decima_rollout_hbm50();  // k_dr_hbm50.hip: 50 executors / 200 jobs
 DecimaRolloutSet decima_rollout_lds();    // k_dr_lds.hip

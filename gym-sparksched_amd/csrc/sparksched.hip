@@ -115,6 +115,40 @@ __global__ __launch_bounds__(64) void k_job_times(const Params* __restrict__ P, 
   }
 }
 
+// Per-env episode statistics (ssim_episode_stats): one wave per env, lanes stride the job records. out[eid][0] = the
+// sum over arrived jobs of min(t_completed, wall) - t_arrival in ms (per-lane partial sums, then a wave tree-sum, f64),
+// [1] = arrived jobs, [2] = completed jobs, [3] = the wall time.
+__global__ __launch_bounds__(64) void k_episode_stats(const Params* __restrict__ P, const uint8_t* state,
+                                                      double* __restrict__ out) {
+  using W = WaveHip;
+  const int eid = blockIdx.x, J = P->L.job_cap;
+  const uint8_t* hot = state + kParamsReserve + (int64_t)eid * P->L.env_bytes;
+  const double wall = W::uni(reinterpret_cast<const EnvHeader*>(hot)->wall);
+  const JobRec* jr = reinterpret_cast<const JobRec*>(hot + P->O.jobs);
+  const JobTimes* jt = reinterpret_cast<const JobTimes*>(hot + P->O.jtimes);
+  double sum = 0.0;
+  int arrived = 0, completed = 0;
+  for (int j = W::lane(); j < J; j += 64) {
+    const int st = jr[j].state;
+    if (st != kJobPending) {
+      const double td = jt[j].tdone;
+      sum += (td < wall ? td : wall) - jt[j].tarr;
+      ++arrived;
+      completed += st == kJobDone;
+    }
+  }
+  sum = W::sum_d(sum);
+  arrived = (int)W::sum_d((double)arrived);  // (counts <= job_cap: exact)
+  completed = (int)W::sum_d((double)completed);
+  if (W::lane() == 0) {
+    double* o = out + (int64_t)eid * 4;
+    o[0] = sum;
+    o[1] = (double)arrived;
+    o[2] = (double)completed;
+    o[3] = wall;
+  }
+}
+
 // Kernel variant for a layout: LDS-resident instantiations specialised on the benchmark shape (BASELINE configs[1]:
 // 10 executors, 50 jobs): fully (stage cap too) when the packed dataset's cap is the synthetic set's 50 x 18, else
 // on (executors, jobs) with the stage cap read at run time (any other TPC-H-format dataset, e.g. the real traces
@@ -146,6 +180,13 @@ static DecimaRolloutSet pick_decima(const Params& p) {
                                                                                           : decima_rollout_lds())
          : !decima_shape(p) || generic_forced()   ? decima_rollout_hbm()
                                                   : decima_rollout_hbm50();
+}
+// The greedy kernel of the unit pick_decima selects (same layout rule, same LDS plan, same waves).
+static DecimaGreedySet pick_decima_greedy(const Params& p) {
+  return p.O.lds_resident                        ? (decima_shape(p) && !generic_forced() ? decima_greedy_lds50()
+                                                                                        : decima_greedy_lds())
+         : !decima_shape(p) || generic_forced() ? decima_greedy_hbm()
+                                                : decima_greedy_hbm50();
 }
 // The priority kinds (SJF / SJF-CP) run k_rollout_prio, which exists for the two run-time-shape engines only.
 static bool prio_kind(int32_t kind) { return kind == SSIM_POLICY_SJF || kind == SSIM_POLICY_SJF_CP; }
@@ -360,6 +401,9 @@ static int rollout_launch(ssim_handle* h, int32_t kind, uint64_t seed, int32_t n
   if (kind == SSIM_POLICY_SJF_CP && h->params.C.max_stages > kPrioMaxStages)
     return set_err(SSIM_E_ARG, "ssim_rollout: SSIM_POLICY_SJF_CP supports at most %d stages per job (max_stages %d)",
                    kPrioMaxStages, h->params.C.max_stages);
+  if (flags & SSIM_ROLLOUT_GREEDY)
+    return set_err(SSIM_E_ARG, "ssim_rollout_ex: SSIM_ROLLOUT_GREEDY is a flag of ssim_decima_rollout only (the "
+                   "heuristic kinds have no sampled / greedy modes; flags 0x%x)", flags);
   if ((flags & ~(SSIM_ROLLOUT_AUTORESET | SSIM_ROLLOUT_PREEMPT | SSIM_ROLLOUT_WARMUP)) != 0)
     return set_err(SSIM_E_ARG, "ssim_rollout_ex: unknown flags 0x%x", flags);
   if ((flags & SSIM_ROLLOUT_PREEMPT) && budget <= 0)
@@ -464,6 +508,13 @@ extern "C" int ssim_decima_profile_next(ssim_handle* h, uint64_t* prof_out) {
 }
 #endif
 
+extern "C" int ssim_episode_stats(ssim_handle* h, double* out, void* stream) {
+  if (h == nullptr || out == nullptr) return set_err(SSIM_E_ARG, "ssim_episode_stats: null argument");
+  hipLaunchKernelGGL(k_episode_stats, dim3(h->params.L.num_envs), dim3(64), 0, (hipStream_t)stream, dparams(h),
+                     h->state, out);
+  return hip_check(hipGetLastError(), "k_episode_stats launch");
+}
+
 extern "C" int ssim_job_times(ssim_handle* h, double* t_arrival, double* t_completed, int32_t* state, void* stream) {
   if (h == nullptr) return set_err(SSIM_E_ARG, "ssim_job_times: null handle");
   hipLaunchKernelGGL(k_job_times, dim3(h->params.L.num_envs), dim3(64), 0, (hipStream_t)stream, dparams(h), h->state,
@@ -494,6 +545,7 @@ static const char* debug_variant(const ssim_handle* h, int32_t variant, SetTrace
 }
 
 extern "C" const char* ssim_debug_kernel_name(const ssim_handle* h, int32_t variant) {
+  if (h != nullptr && variant == SSIM_DEBUG_DECIMA_GREEDY) return pick_decima_greedy(h->params).name;  // (a name only)
   if (h != nullptr && variant == SSIM_DEBUG_PRIO) return prio_name(h->params);  // (a name only: no set KAT of its own)
   SetTraceFn fn;
   const char* n = h != nullptr ? debug_variant(h, variant, &fn) : nullptr;
@@ -721,7 +773,13 @@ extern "C" int ssim_decima_rollout(ssim_handle* h, const float* params, int32_t 
                                    void* stream) {
   if (h == nullptr || params == nullptr || workspace == nullptr || max_steps < 0 || total_decisions < 0)
     return set_err(SSIM_E_ARG, "ssim_decima_rollout: bad argument");
-  if ((flags & ~(SSIM_ROLLOUT_AUTORESET | SSIM_ROLLOUT_PREEMPT | SSIM_ROLLOUT_WARMUP | SSIM_ROLLOUT_TEST_REJECT)) != 0)
+  const bool greedy = (flags & SSIM_ROLLOUT_GREEDY) != 0;
+  if (greedy &&
+      (flags & (SSIM_ROLLOUT_AUTORESET | SSIM_ROLLOUT_PREEMPT | SSIM_ROLLOUT_WARMUP | SSIM_ROLLOUT_TEST_REJECT)) != 0)
+    return set_err(SSIM_E_ARG, "ssim_decima_rollout: SSIM_ROLLOUT_GREEDY does not combine with SSIM_ROLLOUT_AUTORESET / "
+                   "PREEMPT / WARMUP / TEST_REJECT (flags 0x%x)", flags);
+  if ((flags & ~(SSIM_ROLLOUT_AUTORESET | SSIM_ROLLOUT_PREEMPT | SSIM_ROLLOUT_WARMUP | SSIM_ROLLOUT_TEST_REJECT |
+                 SSIM_ROLLOUT_GREEDY)) != 0)
     return set_err(SSIM_E_ARG, "ssim_decima_rollout: unknown flags 0x%x", flags);
   if ((flags & SSIM_ROLLOUT_PREEMPT) && total_decisions <= 0)
     return set_err(SSIM_E_ARG, "ssim_decima_rollout: SSIM_ROLLOUT_PREEMPT needs a decision budget");
@@ -735,7 +793,11 @@ extern "C" int ssim_decima_rollout(ssim_handle* h, const float* params, int32_t 
   }
   const ssim_layout& L = h->params.L;
   const DecimaRolloutSet ks = pick_decima(h->params);
-  const DecimaRolloutFn fn = (flags & SSIM_ROLLOUT_WARMUP) ? ks.rollout_warmup : ks.rollout;
+  // (greedy: the plan caps and the waves are those of the sibling unit `ks`; the kernel never sees the flag's bit)
+  const DecimaRolloutFn fn = greedy                         ? pick_decima_greedy(h->params).rollout
+                             : (flags & SSIM_ROLLOUT_WARMUP) ? ks.rollout_warmup
+                                                             : ks.rollout;
+  flags &= ~SSIM_ROLLOUT_GREEDY;
   const DecimaLdsPlan pl = decima_lds_plan(h->params, ks);
   a.plan_cap = pl.cap;
   a.plan_off = pl.off;
@@ -769,6 +831,9 @@ extern "C" int ssim_decima_rollout_timed(ssim_handle* h, const float* params, in
                                          int32_t* action_log, void* stream) {
   if (h == nullptr || params == nullptr || workspace == nullptr || max_steps < 0)
     return set_err(SSIM_E_ARG, "ssim_decima_rollout_timed: bad argument");
+  if (flags & SSIM_ROLLOUT_GREEDY)
+    return set_err(SSIM_E_ARG, "ssim_decima_rollout_timed: SSIM_ROLLOUT_GREEDY is a flag of ssim_decima_rollout only "
+                   "(fixed-duration collection samples; flags 0x%x)", flags);
   if ((flags & (SSIM_ROLLOUT_AUTORESET | SSIM_ROLLOUT_PREEMPT | SSIM_ROLLOUT_WARMUP)) != 0 || total_decisions != 0 ||
       time_limits != nullptr)
     return set_err(SSIM_E_ARG, "ssim_decima_rollout_timed: does not combine with SSIM_ROLLOUT_AUTORESET / PREEMPT / "

@@ -12,8 +12,10 @@ SSIM_ROLLOUT_AUTORESET = 0x1
 SSIM_ROLLOUT_PREEMPT = 0x2
 SSIM_ROLLOUT_WARMUP = 0x4
 SSIM_ROLLOUT_TEST_REJECT = 0x8  # ssim_decima_rollout test hook
+SSIM_ROLLOUT_GREEDY = 0x10  # ssim_decima_rollout only: arg-max actions instead of draws
 SSIM_DEBUG_ENGINE, SSIM_DEBUG_DECIMA, SSIM_DEBUG_KAT_BAD = 0, 1, 2  # ssim_debug_set_trace_ex variants
 SSIM_DEBUG_PRIO = 3  # ssim_debug_kernel_name only: the SJF / SJF-CP rollout unit of a handle
+SSIM_DEBUG_DECIMA_GREEDY = 4  # ssim_debug_kernel_name only: the unit of a SSIM_ROLLOUT_GREEDY launch
 SSIM_ACT_LEAKY_RELU, SSIM_ACT_TANH = 0, 1  # ssim_mlp3_* activations
 SSIM_ERR_SPACE = 0x1
 SSIM_ERR_KEY = 0x2

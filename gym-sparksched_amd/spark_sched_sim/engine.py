@@ -363,6 +363,15 @@ class DeviceEngine:
                                                              self._stream()), "ssim_job_times")
         return ta, tc, st
 
+    def episode_stats(self) -> np.ndarray:
+        """ssim_episode_stats: per env, reduced on the device, float64 [B][4] = the sum over arrived jobs of
+        min(t_completed, wall_time) - t_arrival (ms), the arrived-job count, the completed-job count, the wall time
+        (host copy: the call ends in a synchronising transfer of 32 B per env)."""
+        out = self.torch.empty((self.num_envs, 4), dtype=self.torch.float64, device=self.device)
+        self._native.check(self._native.lib().ssim_episode_stats(self.handle, out.data_ptr(), self._stream()),
+                           "ssim_episode_stats")
+        return out.cpu().numpy()
+
     def decima_features(self, num_tasks_scale: float = 200.0, work_scale: float = 1e5) -> dict:
         """Decima featurisation of the current obs on device (ssim_decima_features); device tensors,
         overwritten by the next call: node_feats f32 [B,S,5], commit_cap i32 [B,J], edge_mask i32 [B,E]
@@ -398,7 +407,8 @@ class DeviceEngine:
         """ssim_decima_rollout: Decima features + fused policy + step per env and decision, in ONE launch.
         params: DecimaScheduler.packed_params() (fp32 device tensor). samples: a DecimaSampleArena (or None).
         flags: 0 = collect until each env's episode ends; _abi.SSIM_ROLLOUT_AUTORESET / PREEMPT (with
-        total_decisions) / WARMUP as ssim_rollout_budget."""
+        total_decisions) / WARMUP as ssim_rollout_budget; _abi.SSIM_ROLLOUT_GREEDY (with none of those) takes the
+        policy's arg-max action at every decision (seed / counter unused)."""
         ws = self.decima_workspace()
         tl = None
         if time_limits is not None:

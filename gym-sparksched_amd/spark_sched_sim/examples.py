@@ -6,6 +6,8 @@ average job duration in seconds (`metrics.avg_job_duration(env) * 1e-3`).
 
     python -m spark_sched_sim.examples --sched fair      # examples.py --sched fair (BASELINE configs[0])
     python -m spark_sched_sim.examples --sched sjf-cp    # shortest job first, critical-path stage choice
+    python -m spark_sched_sim.examples --sched decima --model decima.pt   # a DecimaScheduler.save checkpoint, greedy
+                                                                          # (--sample: draw the actions instead)
 """
 
 from __future__ import annotations
@@ -41,12 +43,47 @@ def run_episode(env_cfg: dict, scheduler, seed: int = 1234, **env_kwargs) -> flo
     return avg
 
 
+class DecimaHostScheduler:
+    """A trained DecimaScheduler as a host scheduler of the one-env facade (the reference's `--sched decima`): the env
+    is wrapped in DecimaEnvWrapper and every decision is `DecimaScheduler.schedule` on its observation, greedy
+    (arg-max) unless `sample`."""
+
+    name = "Decima"
+
+    def __init__(self, model, sample: bool = False, seed: int = 42):
+        import torch
+
+        from .decima import DecimaEnvWrapper
+
+        self.env_wrapper_cls = DecimaEnvWrapper
+        self.model = model
+        self.greedy = not sample
+        self.generator = torch.Generator(device=model.device).manual_seed(seed)
+
+    def schedule(self, obs):
+        return self.model.schedule_obs(obs, greedy=self.greedy, generator=self.generator)
+
+
 def main(argv=None) -> None:
     parser = ArgumentParser(description=__doc__, formatter_class=ArgumentDefaultsHelpFormatter)
-    parser.add_argument("--sched", choices=list(POLICY_KINDS), required=True)
+    parser.add_argument("--sched", choices=list(POLICY_KINDS) + ["decima"], required=True)
     parser.add_argument("--seed", type=int, default=1234)
+    parser.add_argument("--model", default=None, help="--sched decima: a DecimaScheduler.save checkpoint")
+    parser.add_argument("--sample", action="store_true", help="--sched decima: draw the actions (default: arg-max)")
     args = parser.parse_args(argv)
-    scheduler = host_scheduler(args.sched, ENV_CFG["num_executors"], seed=42)
+    if args.sched == "decima":
+        if not args.model:
+            parser.exit(2, "--sched decima needs --model PATH: a checkpoint written by DecimaScheduler.save (see "
+                           "scripts/train_and_evaluate.py)\n")
+        from .schedulers.decima import DecimaScheduler
+
+        model = DecimaScheduler.load(args.model)
+        if model.num_executors != ENV_CFG["num_executors"]:
+            parser.exit(2, f"{args.model}: trained for {model.num_executors} executors, this example's env has "
+                           f"{ENV_CFG['num_executors']}\n")
+        scheduler = DecimaHostScheduler(model, sample=args.sample, seed=42)
+    else:
+        scheduler = host_scheduler(args.sched, ENV_CFG["num_executors"], seed=42)
     print(f"Example: {scheduler.name} Scheduler")
     print("Env settings:")
     pprint(ENV_CFG)

@@ -46,6 +46,7 @@ def lib() -> ct.CDLL:
     L.ssim_decima_policy.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, u64, u64, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                      vp]
     L.ssim_job_times.argtypes = [vp, vp, vp, vp, vp]
+    L.ssim_episode_stats.argtypes = [vp, vp, vp]
     L.ssim_decima_features.argtypes = [vp, ct.c_float, ct.c_float, vp, vp, vp, vp, vp]
     L.ssim_decima_workspace_bytes.argtypes = [vp]
     L.ssim_decima_workspace_bytes.restype = ct.c_int64
@@ -86,7 +87,7 @@ def lib() -> ct.CDLL:
     L.ssim_discounted_returns.restype = ct.c_int
     for name in ("ssim_layout_for", "ssim_create", "ssim_destroy", "ssim_reset", "ssim_step", "ssim_policy",
                  "ssim_rollout", "ssim_rollout_ex", "ssim_rollout_budget", "ssim_rollout_steps", "ssim_reset_sampled",
-                 "ssim_job_times", "ssim_decima_features", "ssim_decima_policy", "ssim_decima_rollout",
+                 "ssim_job_times", "ssim_episode_stats", "ssim_decima_features", "ssim_decima_policy", "ssim_decima_rollout",
                  "ssim_decima_rollout_timed"):
         getattr(L, name).restype = ct.c_int
     _lib = L
@@ -100,7 +101,7 @@ def check(rc: int, what: str) -> None:
 
 EXPORTED_SYMBOLS = ["ssim_layout_for", "ssim_create", "ssim_destroy", "ssim_reset", "ssim_step", "ssim_policy",
                     "ssim_rollout", "ssim_rollout_ex", "ssim_rollout_budget", "ssim_rollout_steps", "ssim_reset_sampled",
-                    "ssim_job_times",
+                    "ssim_job_times", "ssim_episode_stats",
                     "ssim_decima_features", "ssim_decima_policy", "ssim_decima_workspace_bytes", "ssim_decima_rollout",
                     "ssim_decima_rollout_timed", "ssim_decima_rollout_lds_bytes", "ssim_debug_decima_plan",
                     "ssim_last_error", "ssim_build_id", "ssim_debug_set_trace", "ssim_debug_set_trace_ex",

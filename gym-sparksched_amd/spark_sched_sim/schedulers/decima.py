@@ -29,6 +29,7 @@ Parity: tests/test_decima_policy.py compares both against the per-observation CP
 
 from __future__ import annotations
 
+from copy import deepcopy
 from dataclasses import dataclass
 from typing import Any
 
@@ -42,6 +43,7 @@ from .linear import HipLinear, HipMlp3  # noqa: E402
 NUM_NODE_FEATURES = 5  # env_wrapper.py:9
 NUM_DAG_FEATURES = 3   # scheduler.py:34
 DECIMA_PARAMS = 20802  # parameters of the decima_tpch.yaml architecture (the fused kernel's; csrc/decima_policy.h)
+CHECKPOINT_VERSION = 1  # DecimaScheduler.save / load file format
 
 
 def make_mlp(input_dim: int, hid_dims: list[int], output_dim: int, act_cls: str,
@@ -373,6 +375,54 @@ def gumbel_pick(logp: torch.Tensor, seg: torch.Tensor, nseg: int, generator=None
     return out.scatter_reduce(0, seg, cand, reduce="amax", include_self=True)
 
 
+def argmax_pick(scores: torch.Tensor, mask: torch.Tensor, seg: torch.Tensor, nseg: int) -> torch.Tensor:
+    """The arg-max row per segment over the masked rows: the FIRST row holding the segment's maximum (ties between
+    equal scores go to the lowest index, the device's greedy rule); -1 for segments without a candidate."""
+    s = torch.where(mask, scores, torch.full_like(scores, -torch.inf))
+    best = torch.full((nseg,), -torch.inf, dtype=s.dtype, device=s.device)
+    best = best.scatter_reduce(0, seg, s, reduce="amax", include_self=True)
+    rows = torch.arange(s.numel(), device=s.device)
+    none = s.numel()
+    cand = torch.where((s == best[seg]) & mask, rows, torch.full_like(rows, none))
+    out = torch.full((nseg,), none, dtype=torch.long, device=s.device)
+    out = out.scatter_reduce(0, seg, cand, reduce="amin", include_self=True)
+    return torch.where(out == none, torch.full_like(out, -1), out)
+
+
+def batch_from_obs(obs: dict, device=None) -> DagBatch:
+    """The one-env DagBatch of a reference-format Decima observation (DecimaEnvWrapper: "dag_batch", "dag_ptr",
+    "stage_mask", "exec_mask", "edge_masks"), for `DecimaScheduler.schedule`."""
+    import numpy as np
+
+    i64 = dict(dtype=torch.long, device=device)
+    g = obs["dag_batch"]
+    x = torch.as_tensor(np.asarray(g.nodes, dtype=np.float32).reshape(-1, NUM_NODE_FEATURES), device=device)
+    n = x.shape[0]
+    links = np.asarray(g.edge_links, dtype=np.int64).reshape(-1, 2)
+    ne = links.shape[0]
+    em = np.asarray(obs["edge_masks"], dtype=bool)
+    levels = em.shape[0] if em.ndim == 2 else 0
+    em = em.reshape(levels, ne)
+    bits = np.zeros(ne, dtype=np.int64)
+    for lvl in range(levels):
+        bits |= em[lvl].astype(np.int64) << lvl
+    ptr = torch.as_tensor(np.asarray(obs["dag_ptr"], dtype=np.int64), device=device)
+    nj = ptr.numel() - 1
+    counts = ptr[1:] - ptr[:-1]
+    stage_mask = torch.as_tensor(np.asarray(obs["stage_mask"], dtype=bool).reshape(n), device=device)
+    exec_cap = torch.as_tensor(np.asarray(obs["exec_mask"], dtype=bool).reshape(nj, -1).sum(axis=1).astype(np.int64),
+                               device=device)
+    zeros_n = torch.zeros(n, **i64)
+    return DagBatch(x=x, edge_index=torch.as_tensor(links.T.copy(), device=device).reshape(2, ne),
+                    edge_bits=torch.as_tensor(bits.astype(np.int32), device=device), max_levels=levels,
+                    env_levels=torch.tensor([levels if n > 0 else 0], **i64), ptr=ptr,
+                    node_dag=torch.repeat_interleave(torch.arange(nj, **i64), counts, output_size=n),
+                    node_env=zeros_n, dag_env=torch.zeros(nj, **i64), obs_ptr=torch.tensor([0, nj], **i64),
+                    stage_mask=stage_mask, exec_cap=exec_cap,
+                    num_stage_acts=stage_mask.long().sum().reshape(1), num_nodes=torch.tensor([n], **i64),
+                    num_edges=torch.tensor([ne], **i64), num_envs=1, max_nodes=n)
+
+
 class NodeEncoder(nn.Module):
     """scheduler.py:176-245 (reverse flow: children send to parents, deepest level first). Each level runs
     mlp_msg on every node and sums child messages into parents with the level's 0/1 edge weights: the same
@@ -555,6 +605,10 @@ class DecimaScheduler(nn.Module):
         policy_mlp_kwargs = policy_mlp_kwargs or {"hid_dims": [64, 64], "act_cls": "Tanh"}
         self.name = "Decima"
         self.num_executors = num_executors
+        # the architecture as save() records it (builtins only: the checkpoint loads with weights_only=True)
+        self._arch = {"embed_dim": int(embed_dim), "gnn_mlp_kwargs": deepcopy(gnn_mlp_kwargs),
+                      "policy_mlp_kwargs": deepcopy(policy_mlp_kwargs), "num_node_features": int(num_node_features),
+                      "num_dag_features": int(num_dag_features)}
         self.max_grad_norm = max_grad_norm
         self.encoder = EncoderNetwork(num_node_features, embed_dim, gnn_mlp_kwargs)
         emb = {"node": embed_dim, "dag": embed_dim, "glob": embed_dim}
@@ -574,13 +628,16 @@ class DecimaScheduler(nn.Module):
         return torch.cumsum(b.stage_mask.long(), 0) - 1 - _excl(b.num_stage_acts)[b.node_env]
 
     @torch.no_grad()
-    def schedule(self, b: DagBatch, generator=None, stream: tuple | None = None) -> dict[str, torch.Tensor]:
+    def schedule(self, b: DagBatch, generator=None, stream: tuple | None = None,
+                 greedy: bool = False) -> dict[str, torch.Tensor]:
         """One decision per env (envs with no schedulable stage get stage_idx -1, num_exec 1). Returns device
         tensors: stage_idx i32 [B] (index among the env's schedulable stages), num_exec i32 [B] (already
         1 + the sampled exec action, DecimaActWrapper.action), job_idx i64 [B] (DAG index within the env),
         exec_idx i64 [B], lgprob f32 [B] (utils.sample: log of the softmax probability, stage + exec).
         `stream` = (seed, counter, global env ids i64 [B]) draws the Gumbel noise from counter_uniform
-        instead of `generator` (rank-independent sampling)."""
+        instead of `generator` (rank-independent sampling). greedy: both choices are the arg-max of their scores (the
+        first maximal index: the lowest schedulable node, the lowest exec action) instead of draws; the dict is the
+        same, lgprob being the log-probability of the chosen pair."""
         B = b.num_envs
         dev = b.x.device
         h = self.encoder(b, per_obs_no_mp=True)
@@ -595,7 +652,10 @@ class DecimaScheduler(nn.Module):
             N = self.num_executors
             u_exec = counter_uniform(seed, counter, env_ids[:, None].expand(B, N).reshape(-1),
                                      torch.arange(N, device=dev).repeat(B), 1)
-        pick = gumbel_pick(logp, b.node_env, B, generator, u=u_stage)  # flat node row per env
+        if greedy:
+            pick = argmax_pick(scores, b.stage_mask, b.node_env, B)
+        else:
+            pick = gumbel_pick(logp, b.node_env, B, generator, u=u_stage)  # flat node row per env
         live = pick >= 0
         row = pick.clamp(min=0)
         stage_idx = torch.where(live, self._sched_rows(b)[row] if row.numel() and b.x.shape[0] else pick, -1)
@@ -606,7 +666,10 @@ class DecimaScheduler(nn.Module):
         elogp = torch.where(valid, elogp, torch.full_like(elogp, -torch.inf))
         N = self.num_executors
         seg = torch.arange(B, device=dev)[:, None].expand(B, N).reshape(-1)
-        epick = gumbel_pick(elogp.reshape(-1), seg, B, generator, u=u_exec)
+        if greedy:
+            epick = argmax_pick(es.reshape(-1), valid.reshape(-1), seg, B)
+        else:
+            epick = gumbel_pick(elogp.reshape(-1), seg, B, generator, u=u_exec)
         ok = live & (epick >= 0)
         exec_idx = torch.where(ok, epick - envs * N, torch.zeros_like(epick))
         lg_stage = torch.where(live, logp[row] if b.x.shape[0] else torch.zeros(B, device=dev),
@@ -615,6 +678,42 @@ class DecimaScheduler(nn.Module):
         return {"stage_idx": stage_idx.to(torch.int32), "num_exec": (exec_idx + 1).to(torch.int32),
                 "job_idx": torch.where(live, dags - b.obs_ptr[:-1], torch.full_like(dags, -1)),
                 "exec_idx": exec_idx, "lgprob": (lg_stage + lg_exec).float()}
+
+    def schedule_obs(self, obs: dict, greedy: bool = False, generator=None):
+        """The reference's `schedule(obs)` for one DecimaEnvWrapper observation: (action, info) with the action in
+        DecimaActWrapper's format ({"stage_idx", "num_exec"}: num_exec is the exec action, the wrapper adds 1)."""
+        out = self.schedule(batch_from_obs(obs, self.device), generator=generator, greedy=greedy)
+        action = {"stage_idx": int(out["stage_idx"][0]), "num_exec": int(out["exec_idx"][0])}
+        return action, {"lgprob": float(out["lgprob"][0]), "job_idx": int(out["job_idx"][0])}
+
+    def save(self, path) -> None:
+        """Writes a checkpoint: a torch.save of a plain dict (tensors and builtins only) holding the format version,
+        num_executors, the architecture kwargs and the state_dict. `load` reads it with weights_only=True."""
+        state = {k: v.detach().cpu().clone() for k, v in self.state_dict().items()}
+        torch.save({"format_version": CHECKPOINT_VERSION, "num_executors": int(self.num_executors),
+                    "arch": deepcopy(self._arch), "state_dict": state}, path)
+
+    @classmethod
+    def load(cls, path, device=None) -> "DecimaScheduler":
+        """A DecimaScheduler from a `save` checkpoint (read with torch.load(weights_only=True): no pickled code runs),
+        on `device`. ValueError for a file of another format version, or of another architecture than the fused
+        kernels' (DECIMA_PARAMS parameters: the decima_tpch.yaml networks)."""
+        ck = torch.load(path, map_location="cpu", weights_only=True)
+        if not isinstance(ck, dict) or "format_version" not in ck:
+            raise ValueError(f"{path}: not a DecimaScheduler checkpoint (no format_version)")
+        if ck["format_version"] != CHECKPOINT_VERSION:
+            raise ValueError(f"{path}: checkpoint format version {ck['format_version']}, this build reads "
+                             f"{CHECKPOINT_VERSION}")
+        num_params = sum(int(v.numel()) for v in ck["state_dict"].values())
+        if num_params != DECIMA_PARAMS:
+            raise ValueError(f"{path}: architecture with {num_params} parameters, the fused kernels implement the "
+                             f"decima_tpch.yaml architecture ({DECIMA_PARAMS})")
+        sched = cls(int(ck["num_executors"]), **ck["arch"])
+        if sum(p.numel() for p in sched.parameters()) != DECIMA_PARAMS:
+            raise ValueError(f"{path}: architecture kwargs {ck['arch']} do not describe the decima_tpch.yaml "
+                             f"architecture ({DECIMA_PARAMS} parameters)")
+        sched.load_state_dict(ck["state_dict"])
+        return sched.to(device) if device is not None else sched
 
     @torch.no_grad()
     def packed_params(self, dev) -> torch.Tensor:
@@ -629,7 +728,9 @@ class DecimaScheduler(nn.Module):
         """`schedule` for every env of a DeviceEngine in ONE kernel launch (ssim_decima_policy,
         csrc/decima_policy.h): the same forward over the obs arena and the device features, weights read
         from a packed copy of this module's parameters, sampling on a counter-based device stream of
-        (seed, env, counter). Only the decima_tpch.yaml architecture (20802 parameters). Returns the same keys
+        (seed, env, counter). It always samples: the arg-max mode exists in `schedule(greedy=True)` and in the
+        persistent rollout (DeviceEngine.decima_rollout with _abi.SSIM_ROLLOUT_GREEDY), not in this lockstep kernel.
+        Only the decima_tpch.yaml architecture (20802 parameters). Returns the same keys
         as `schedule` (int32/float32 device tensors); with_scores adds per-env stage scores [B, stage_cap]
         and exec scores [B, N]."""
         from .. import native

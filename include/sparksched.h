@@ -222,6 +222,14 @@ int ssim_rollout(ssim_handle* h, int32_t kind, uint64_t seed, int32_t num_steps,
 /* ssim_decima_rollout only, a test hook: the launch's first decision of every env asks for N + 1 executors, an action
  * the env refuses (the env freezes with SSIM_ERR_INVARIANT and the sample recorded for it is dropped). */
 #define SSIM_ROLLOUT_TEST_REJECT 0x8
+/* ssim_decima_rollout only: every decision is the policy's arg-max action instead of a draw (evaluating a policy). The
+ * scores, the log-softmax and the recorded lgprob (of the chosen pair) are those of the sampled mode; seed and counter
+ * are ignored. Ties between bit-equal fp32 scores go to the lowest schedulable node and to the lowest exec action k.
+ * Combines with a sample arena, an action log, time_limits and max_steps; SSIM_E_ARG with SSIM_ROLLOUT_AUTORESET,
+ * SSIM_ROLLOUT_PREEMPT, SSIM_ROLLOUT_WARMUP or SSIM_ROLLOUT_TEST_REJECT, through ssim_decima_rollout_timed and through
+ * every ssim_rollout* entry. The launch runs the greedy kernel of the unit's sibling
+ * (ssim_debug_kernel_name(h, SSIM_DEBUG_DECIMA_GREEDY)) with that unit's LDS plan and waves. */
+#define SSIM_ROLLOUT_GREEDY 0x10
 int ssim_rollout_ex(ssim_handle* h, int32_t kind, uint64_t seed, int32_t num_steps, int32_t flags,
                     const double* time_limits, int32_t* action_log, void* stream);
 
@@ -245,6 +253,12 @@ int ssim_rollout_steps(ssim_handle* h, int32_t kind, uint64_t seed, const int32_
 /* Per-job results for metrics (spark_sched_sim/metrics.py): t_arrival/t_completed float64 [num_envs][job_cap]
  * and job state int32 [num_envs][job_cap] (0 not arrived, 1 active, 2 completed), any may be NULL. */
 int ssim_job_times(ssim_handle* h, double* t_arrival, double* t_completed, int32_t* state, void* stream);
+
+/* Per-env episode statistics, reduced on the device (what an evaluation needs of ssim_job_times, without copying the
+ * job tables out): out device float64 [num_envs][4] = the sum over arrived jobs (state != 0) of
+ * min(t_completed, wall_time) - t_arrival in ms, the arrived-job count, the completed-job count, the wall time.
+ * The caller divides (no arrived job: 0 / 0). */
+int ssim_episode_stats(ssim_handle* h, double* out, void* stream);
 
 /* Decima observation features from the current obs (replaces DecimaObsWrapper.observation,
  * schedulers/decima/env_wrapper.py:69-143, and make_dag_layer_edge_masks, schedulers/decima/utils.py:238-267).
@@ -323,7 +337,8 @@ int ssim_debug_decima_plan(const ssim_handle* h, int32_t* cap, int32_t* waves);
  *   0: collection — an env stops when its episode ends (terminated, truncated: wall_time >= its time limit);
  *   SSIM_ROLLOUT_AUTORESET: finished episodes are reset in place (time_limits as ssim_rollout_ex) and the env goes on;
  *   SSIM_ROLLOUT_PREEMPT with total_decisions > 0: a shared decision budget as ssim_rollout_budget;
- *   SSIM_ROLLOUT_WARMUP: the launch runs under the symbol k_decima_rollout_warmup (unmeasured launches).
+ *   SSIM_ROLLOUT_WARMUP: the launch runs under the symbol k_decima_rollout_warmup (unmeasured launches);
+ *   SSIM_ROLLOUT_GREEDY: arg-max actions instead of draws (see the flag; with none of the three flags above).
  * total_decisions: 0 = no budget. samples: optional sample arena (NULL = none). action_log: optional int32
  * [max_steps][num_envs][2] (stage_idx, num_exec of every decision started in this launch). */
 int ssim_decima_rollout(ssim_handle* h, const float* params, int32_t num_params, float num_tasks_scale,
@@ -388,6 +403,7 @@ int ssim_debug_set_trace(ssim_handle* h, const int32_t* ops, int32_t n_ops, int3
 #define SSIM_DEBUG_DECIMA 1
 #define SSIM_DEBUG_KAT_BAD 2
 #define SSIM_DEBUG_PRIO 3 /* ssim_debug_kernel_name only: the unit an SJF / SJF-CP rollout on this handle launches */
+#define SSIM_DEBUG_DECIMA_GREEDY 4 /* ssim_debug_kernel_name only: the unit of a SSIM_ROLLOUT_GREEDY launch ("drg_*") */
 int ssim_debug_set_trace_ex(ssim_handle* h, const int32_t* ops, int32_t n_ops, int32_t width, int32_t* orders,
                             int32_t variant, void* stream);
 /* Name of the kernel translation unit a variant selects for this handle ("hbm_n100", "bench900", "dr_hbm50", ...; ""
