@@ -444,28 +444,32 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, SSIM_DR_THREADS(kHelp))
 
 using DecimaRolloutFn = void (*)(const Params*, uint8_t*, uint8_t*, DecimaRolloutArgs, int, int, const double*,
                                  uint8_t*, int32_t*, int64_t, uint64_t*);
-struct DecimaRolloutSet {
-  DecimaRolloutFn rollout, rollout_warmup;
-  SetTraceFn set_trace;  // the set KAT through this unit's engine instantiation (kernels.h k_set_trace)
-  const char* name;      // the translation unit (ssim_debug_kernel_name)
-  int waves = 1;         // waves per env's workgroup (kDpHelpWaves: the exec-score helpers)
-};
 using DecimaTimedFn = void (*)(const Params*, uint8_t*, uint8_t*, DecimaRolloutArgs, ssim_decima_timed, int, int,
                                uint8_t*, int32_t*, uint64_t*);
-// one per k_dr_*.hip unit, with that unit's compile definitions
-DecimaTimedFn decima_timed_hbm();    // k_drt_hbm.hip
-DecimaTimedFn decima_timed_hbm50();  // k_drt_hbm50.hip
-DecimaTimedFn decima_timed_lds();    // k_drt_lds.hip
-DecimaTimedFn decima_timed_lds50();  // k_drt_lds50.hip
-struct DecimaGreedySet {
-  DecimaRolloutFn rollout;
-  const char* name;  // the translation unit (ssim_debug_kernel_name, SSIM_DEBUG_DECIMA_GREEDY)
+// What a k_dr_*.hip unit returns: its kernels, and the set KAT through its engine instantiation (kernels.h k_set_trace).
+struct DecimaRolloutFns {
+  DecimaRolloutFn rollout, rollout_warmup;
+  SetTraceFn set_trace;
 };
-DecimaGreedySet decima_greedy_hbm();    // k_drg_hbm.hip
-DecimaGreedySet decima_greedy_hbm50();  // k_drg_hbm50.hip
-DecimaGreedySet decima_greedy_lds();    // k_drg_lds.hip
-DecimaGreedySet decima_greedy_lds50();  // k_drg_lds50.hip
-DecimaRolloutSet decima_rollout_hbm();    // k_dr_hbm.hip
-DecimaRolloutSet decima_rollout_hbm50();  // k_dr_hbm50.hip: 50 executors / 200 jobs
-DecimaRolloutSet decima_rollout_lds();    // k_dr_lds.hip
-DecimaRolloutSet decima_rollout_lds50();  // k_dr_lds50.hip: 50 executors / 200 jobs
+// One Decima unit (units.h DecimaUnit) as sparksched.hip launches it: the kernels of its k_dr_* / k_drt_* / k_drg_*
+// translation units and the waves per env's workgroup, so a launch takes its kernel, LDS plan and block size from one row.
+struct DecimaUnitRow {
+  DecimaRolloutFn rollout, rollout_warmup;
+  DecimaTimedFn timed;
+  DecimaRolloutFn greedy;
+  SetTraceFn set_trace;
+  int waves;
+};
+// one accessor per translation unit, with that unit's compile definitions
+DecimaRolloutFns decima_rollout_hbm();    // k_dr_hbm.hip
+DecimaRolloutFns decima_rollout_hbm50();  // k_dr_hbm50.hip: 50 executors / 200 jobs
+DecimaRolloutFns decima_rollout_lds();    // k_dr_lds.hip
+DecimaRolloutFns decima_rollout_lds50();  // k_dr_lds50.hip: 50 executors / 200 jobs
+DecimaTimedFn decima_timed_hbm();      // k_drt_hbm.hip
+DecimaTimedFn decima_timed_hbm50();    // k_drt_hbm50.hip
+DecimaTimedFn decima_timed_lds();      // k_drt_lds.hip
+DecimaTimedFn decima_timed_lds50();    // k_drt_lds50.hip
+DecimaRolloutFn decima_greedy_hbm();    // k_drg_hbm.hip
+DecimaRolloutFn decima_greedy_hbm50();  // k_drg_hbm50.hip
+DecimaRolloutFn decima_greedy_lds();    // k_drg_lds.hip
+DecimaRolloutFn decima_greedy_lds50();  // k_drg_lds50.hip

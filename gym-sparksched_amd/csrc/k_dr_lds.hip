@@ -3,5 +3,4 @@
 #define SSIM_DP_PIPELINE 1  // (one wave per SIMD: decima_policy.h dp_layer_in_p)
 #include "decima_rollout.h"
 
-DecimaRolloutSet decima_rollout_lds() { return {k_decima_rollout<true>, k_decima_rollout_warmup<true>, k_set_trace<WaveHip, true, 0, 0, 0, kTagDrLds>,
-          "dr_lds"}; }
+DecimaRolloutFns decima_rollout_lds() { return {k_decima_rollout<true>, k_decima_rollout_warmup<true>, k_set_trace<WaveHip, true, 0, 0, 0, kTagDrLds>}; }

@@ -4,7 +4,7 @@
 #define SSIM_DP_PIPELINE 1  // (one wave per SIMD: decima_policy.h dp_layer_in_p)
 #include "decima_rollout.h"
 
-DecimaRolloutSet decima_rollout_lds50() {
+DecimaRolloutFns decima_rollout_lds50() {
   return {k_decima_rollout<true, 50, 200, true>, k_decima_rollout_warmup<true, 50, 200, true>,
-          k_set_trace<WaveHip, true, 50, 200, 0, kTagDrLds50>, "dr_lds50", kDpHelpWaves};
+          k_set_trace<WaveHip, true, 50, 200, 0, kTagDrLds50>};
 }

@@ -4,4 +4,4 @@
 #define SSIM_EV_PAGES_GENERIC 2
 #include "decima_rollout.h"
 
-DecimaGreedySet decima_greedy_hbm() { return {k_decima_rollout_greedy<false>, "drg_hbm"}; }
+DecimaRolloutFn decima_greedy_hbm() { return k_decima_rollout_greedy<false>; }

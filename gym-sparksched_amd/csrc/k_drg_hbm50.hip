@@ -3,4 +3,4 @@
 #define SSIM_OPAQUE_LANE 1
 #include "decima_rollout.h"
 
-DecimaGreedySet decima_greedy_hbm50() { return {k_decima_rollout_greedy<false, 50, 200>, "drg_hbm50"}; }
+DecimaRolloutFn decima_greedy_hbm50() { return k_decima_rollout_greedy<false, 50, 200>; }

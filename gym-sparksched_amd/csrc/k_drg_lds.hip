@@ -3,4 +3,4 @@
 #define SSIM_DP_PIPELINE 1  // (one wave per SIMD: decima_policy.h dp_layer_in_p)
 #include "decima_rollout.h"
 
-DecimaGreedySet decima_greedy_lds() { return {k_decima_rollout_greedy<true>, "drg_lds"}; }
+DecimaRolloutFn decima_greedy_lds() { return k_decima_rollout_greedy<true>; }

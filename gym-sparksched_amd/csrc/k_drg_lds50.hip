@@ -4,4 +4,4 @@
 #define SSIM_DP_PIPELINE 1  // (one wave per SIMD: decima_policy.h dp_layer_in_p)
 #include "decima_rollout.h"
 
-DecimaGreedySet decima_greedy_lds50() { return {k_decima_rollout_greedy<true, 50, 200, true>, "drg_lds50"}; }
+DecimaRolloutFn decima_greedy_lds50() { return k_decima_rollout_greedy<true, 50, 200, true>; }

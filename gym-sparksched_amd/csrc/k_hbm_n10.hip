@@ -6,4 +6,4 @@
 #define SSIM_OPAQUE_LANE 1
 #include "kernels.h"
 
-KernelSet kernels_hbm_n10() { return kernel_set<false, 10, 50, 0, kTagHbmN10>("hbm_n10"); }
+KernelSet kernels_hbm_n10() { return kernel_set<false, 10, 50, 0, kTagHbmN10>(); }

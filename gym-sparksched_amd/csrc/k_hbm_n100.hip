@@ -6,7 +6,7 @@
 #define SSIM_OPAQUE_LANE 1
 #include "kernels.h"
 
-KernelSet kernels_hbm_n100() { return kernel_set<false, 100, 200, 0, kTagHbmN100>("hbm_n100"); }
+KernelSet kernels_hbm_n100() { return kernel_set<false, 100, 200, 0, kTagHbmN100>(); }
 
 // the set KAT's known-bad variant (tests/test_gpu_sets.py): the same instantiation on the test-only wave type that
 // reproduces the ROCm 7.2 page-assembly miscompile (engine.h KatBadPage); it must FAIL the KAT

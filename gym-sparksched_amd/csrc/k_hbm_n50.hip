@@ -5,4 +5,4 @@
 #define SSIM_OPAQUE_LANE 1
 #include "kernels.h"
 
-KernelSet kernels_hbm_n50() { return kernel_set<false, 50, 200, 0, kTagHbmN50>("hbm_n50"); }
+KernelSet kernels_hbm_n50() { return kernel_set<false, 50, 200, 0, kTagHbmN50>(); }

@@ -2,7 +2,7 @@
 //
 // Each instantiation of the engine is a large kernel, so they are compiled in separate translation units
 // (k_*.hip, built in parallel) that each return the kernel pointers of one layout specialisation
-// (KernelSet); sparksched.hip picks one per launch from the layout.
+// (KernelSet); sparksched.hip keeps them in a table indexed by the unit that units.h names for a layout.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -246,18 +246,17 @@ struct KernelSet {
   StepFn step;
   RolloutFn rollout, rollout_warmup;
   SetTraceFn set_trace;  // the set KAT through this unit's engine instantiation (k_set_trace)
-  const char* name;      // the translation unit (ssim_debug_kernel_name)
 };
 template <bool kRes, int kN, int kJ, int kS, int kTag>
-inline KernelSet kernel_set(const char* name) {
+inline KernelSet kernel_set() {
   return {k_step<kRes, kN, kJ, kS>, k_rollout<kRes, kN, kJ, kS>, k_rollout_warmup<kRes, kN, kJ, kS>,
-          k_set_trace<WaveHip, kRes, kN, kJ, kS, kTag>, name};
+          k_set_trace<WaveHip, kRes, kN, kJ, kS, kTag>};
 }
 // Translation-unit tags of k_set_trace (one per k_*.hip)
 enum : int { kTagBench900 = 1, kTagBench, kTagLds, kTagHbm, kTagHbmN100, kTagHbmN10, kTagHbmN50, kTagDrHbm, kTagDrHbm50,
              kTagDrLds, kTagKatBad, kTagDrLds50 };
 SetTraceFn set_trace_kat_bad();  // k_hbm_n100.hip: the N = 100 / J = 200 instantiation on WaveHipKatBadPage
-// one per translation unit
+// one per translation unit (units.h EngineUnit)
 KernelSet kernels_bench900();  // k_bench900.hip: LDS-resident, 10 executors / 50 jobs / stage cap 900
 KernelSet kernels_bench();     // k_bench.hip: LDS-resident, 10 executors / 50 jobs, stage cap at run time
 KernelSet kernels_lds();       // k_lds.hip: LDS-resident, any shape

@@ -20,6 +20,7 @@
 #include "decima.h"
 #include "decima_policy.h"
 #include "decima_rollout.h"
+#include "units.h"
 
 // ------------------------------------------------------------------------------------------ kernels
 
@@ -149,14 +150,8 @@ __global__ __launch_bounds__(64) void k_episode_stats(const Params* __restrict__
   }
 }
 
-// Kernel variant for a layout: LDS-resident instantiations specialised on the benchmark shape (BASELINE configs[1]:
-// 10 executors, 50 jobs): fully (stage cap too) when the packed dataset's cap is the synthetic set's 50 x 18, else
-// on (executors, jobs) with the stage cap read at run time (any other TPC-H-format dataset, e.g. the real traces
-// loaded from data/tpch); other shapes use the generic instantiations.
-static bool bench_shape(const Params& p) { return p.L.num_executors == 10 && p.L.job_cap == 50; }
-static bool decima_shape(const Params& p) { return p.L.num_executors == 50 && p.L.job_cap == 200; }
-static bool large_shape(const Params& p) { return p.L.num_executors == 100 && p.L.job_cap == 200; }
-// Diagnostic switch: SSIM_GENERIC=1 runs every HBM-resident layout on the generic (run-time shape) kernels.
+// Kernel unit of a layout: units.h has the rule and the names, the tables here the kernels, one row per unit.
+// Diagnostic switch: SSIM_GENERIC=1 runs the generic (run-time shape) kernels where units.h says so.
 static bool generic_forced() {
   static const int on = [] {
     const char* v = getenv("SSIM_GENERIC");
@@ -164,41 +159,46 @@ static bool generic_forced() {
   }();
   return on != 0;
 }
-static KernelSet pick_kernels(const Params& p) {
-  if (!p.O.lds_resident) {  // HBM-resident: the configs[2] / [3] shapes have (executors, jobs)-specialised kernels
-    if (generic_forced()) return kernels_hbm();
-    if (large_shape(p)) return kernels_hbm_n100();
-    if (decima_shape(p)) return kernels_hbm_n50();
-    if (bench_shape(p)) return kernels_hbm_n10();
-    return kernels_hbm();
-  }
-  if (bench_shape(p)) return p.L.stage_cap == 900 ? kernels_bench900() : kernels_bench();
-  return kernels_lds();
+template <class Unit>
+static Unit unit_of(const Params& p, Unit (*rule)(const ssim_layout&, bool, bool)) {
+  return rule(p.L, p.O.lds_resident != 0, generic_forced());
 }
-static DecimaRolloutSet pick_decima(const Params& p) {
-  return p.O.lds_resident                          ? (decima_shape(p) && !generic_forced() ? decima_rollout_lds50()
-                                                                                          : decima_rollout_lds())
-         : !decima_shape(p) || generic_forced()   ? decima_rollout_hbm()
-                                                  : decima_rollout_hbm50();
+static const KernelSet& pick_kernels(const Params& p) {
+  struct Table {
+    KernelSet row[kNumEngineUnits];
+    Table() {
+      row[kEngBench900] = kernels_bench900(), row[kEngBench] = kernels_bench(), row[kEngLds] = kernels_lds();
+      row[kEngHbm] = kernels_hbm(), row[kEngHbmN100] = kernels_hbm_n100(), row[kEngHbmN50] = kernels_hbm_n50();
+      row[kEngHbmN10] = kernels_hbm_n10();
+    }
+  };
+  static const Table t;
+  return t.row[unit_of(p, engine_unit)];
 }
-// The greedy kernel of the unit pick_decima selects (same layout rule, same LDS plan, same waves).
-static DecimaGreedySet pick_decima_greedy(const Params& p) {
-  return p.O.lds_resident                        ? (decima_shape(p) && !generic_forced() ? decima_greedy_lds50()
-                                                                                        : decima_greedy_lds())
-         : !decima_shape(p) || generic_forced() ? decima_greedy_hbm()
-                                                : decima_greedy_hbm50();
+static_assert(kDecimaHelpWaves == kDpHelpWaves, "units.h states the helper waves of dr_lds50");
+static const DecimaUnitRow& pick_decima(const Params& p) {
+  struct Table {
+    DecimaUnitRow row[kNumDecimaUnits];
+    void set(DecimaUnit u, DecimaRolloutFns k, DecimaTimedFn timed, DecimaRolloutFn greedy) {
+      row[u] = DecimaUnitRow{k.rollout, k.rollout_warmup, timed, greedy, k.set_trace, decima_unit_waves(u)};
+    }
+    Table() {
+      set(kDrHbm, decima_rollout_hbm(), decima_timed_hbm(), decima_greedy_hbm());
+      set(kDrHbm50, decima_rollout_hbm50(), decima_timed_hbm50(), decima_greedy_hbm50());
+      set(kDrLds, decima_rollout_lds(), decima_timed_lds(), decima_greedy_lds());
+      set(kDrLds50, decima_rollout_lds50(), decima_timed_lds50(), decima_greedy_lds50());
+    }
+  };
+  static const Table t;
+  return t.row[unit_of(p, decima_unit)];
 }
 // The priority kinds (SJF / SJF-CP) run k_rollout_prio, which exists for the two run-time-shape engines only.
 static bool prio_kind(int32_t kind) { return kind == SSIM_POLICY_SJF || kind == SSIM_POLICY_SJF_CP; }
-static RolloutFn pick_prio(const Params& p) { return p.O.lds_resident ? rollout_prio_lds() : rollout_prio_hbm(); }
-static const char* prio_name(const Params& p) { return p.O.lds_resident ? "prio_lds" : "prio_hbm"; }
+static RolloutFn pick_prio(const Params& p) {
+  return unit_of(p, prio_unit) == kPrioLds ? rollout_prio_lds() : rollout_prio_hbm();
+}
 static bool known_kind(int32_t kind) {
   return kind == SSIM_POLICY_FAIR || kind == SSIM_POLICY_FIFO || kind == SSIM_POLICY_RANDOM || prio_kind(kind);
-}
-static StepFn pick_step(const Params& p) { return pick_kernels(p).step; }
-static RolloutFn pick_rollout(const Params& p, bool warmup = false) {
-  const KernelSet k = pick_kernels(p);
-  return warmup ? k.rollout_warmup : k.rollout;
 }
 
 // ------------------------------------------------------------------------------------------ C ABI
@@ -372,7 +372,7 @@ extern "C" int ssim_reset(ssim_handle* h, void* stream) {
 extern "C" int ssim_step(ssim_handle* h, const int32_t* stage_idx, const int32_t* num_exec, void* stream) {
   if (h == nullptr || stage_idx == nullptr || num_exec == nullptr) return set_err(SSIM_E_ARG, "ssim_step: null");
   const ssim_layout& L = h->params.L;
-  const StepFn fn = pick_step(h->params);
+  const StepFn fn = pick_kernels(h->params).step;
   const int rc = lds_opt_in((const void*)fn, h->params.O.lds_bytes);
   if (rc != SSIM_OK) return rc;
   hipLaunchKernelGGL(fn, dim3(L.num_envs), dim3(64), (size_t)h->params.O.lds_bytes, (hipStream_t)stream,
@@ -393,9 +393,20 @@ extern "C" int ssim_policy(ssim_handle* h, int32_t kind, uint64_t seed, uint64_t
   return hip_check(hipGetLastError(), "k_policy launch");
 }
 
+// The flag checks every rollout entry shares (`who` names the entry in messages, `allowed` its flag bits).
+static int check_rollout_flags(const char* who, const ssim_handle* h, int32_t flags, int32_t allowed, int64_t budget) {
+  if ((flags & ~allowed) != 0) return set_err(SSIM_E_ARG, "%s: unknown flags 0x%x", who, flags);
+  if ((flags & SSIM_ROLLOUT_PREEMPT) && budget <= 0)
+    return set_err(SSIM_E_ARG, "%s: SSIM_ROLLOUT_PREEMPT needs a decision budget", who);
+  if ((flags & SSIM_ROLLOUT_AUTORESET) && !(h->params.C.job_arrival_gap > 0.0))
+    return set_err(SSIM_E_ARG, "%s: auto-reset needs job_arrival_gap in the config", who);
+  return SSIM_OK;
+}
+
+// prof_out: -DSSIM_PROFILE builds' per-wave phase cycle sums, [num_envs][kNumPhases] (else null).
 static int rollout_launch(ssim_handle* h, int32_t kind, uint64_t seed, int32_t num_steps, int64_t budget,
                           int32_t flags, const double* time_limits, int32_t* action_log, void* stream,
-                          const int32_t* env_steps = nullptr) {
+                          const int32_t* env_steps = nullptr, uint64_t* prof_out = nullptr) {
   if (h == nullptr || num_steps < 0 || budget < 0) return set_err(SSIM_E_ARG, "ssim_rollout: bad argument");
   if (!known_kind(kind)) return set_err(SSIM_E_ARG, "ssim_rollout: unknown policy %d", kind);
   if (kind == SSIM_POLICY_SJF_CP && h->params.C.max_stages > kPrioMaxStages)
@@ -404,14 +415,11 @@ static int rollout_launch(ssim_handle* h, int32_t kind, uint64_t seed, int32_t n
   if (flags & SSIM_ROLLOUT_GREEDY)
     return set_err(SSIM_E_ARG, "ssim_rollout_ex: SSIM_ROLLOUT_GREEDY is a flag of ssim_decima_rollout only (the "
                    "heuristic kinds have no sampled / greedy modes; flags 0x%x)", flags);
-  if ((flags & ~(SSIM_ROLLOUT_AUTORESET | SSIM_ROLLOUT_PREEMPT | SSIM_ROLLOUT_WARMUP)) != 0)
-    return set_err(SSIM_E_ARG, "ssim_rollout_ex: unknown flags 0x%x", flags);
-  if ((flags & SSIM_ROLLOUT_PREEMPT) && budget <= 0)
-    return set_err(SSIM_E_ARG, "ssim_rollout: SSIM_ROLLOUT_PREEMPT needs a decision budget (ssim_rollout_budget)");
-  if ((flags & SSIM_ROLLOUT_AUTORESET) && !(h->params.C.job_arrival_gap > 0.0))
-    return set_err(SSIM_E_ARG, "ssim_rollout_ex: auto-reset needs job_arrival_gap in the config");
+  const int rc0 = check_rollout_flags("ssim_rollout_ex", h, flags,
+                                      SSIM_ROLLOUT_AUTORESET | SSIM_ROLLOUT_PREEMPT | SSIM_ROLLOUT_WARMUP, budget);
+  if (rc0 != SSIM_OK) return rc0;
   const ssim_layout& L = h->params.L;
-  const KernelSet ks = pick_kernels(h->params);
+  const KernelSet& ks = pick_kernels(h->params);
   const RolloutFn fn = prio_kind(kind) ? pick_prio(h->params)  // (one symbol: warm-up launches included)
                                        : (flags & SSIM_ROLLOUT_WARMUP) ? ks.rollout_warmup : ks.rollout;
   const int64_t lds = h->params.O.lds_bytes;
@@ -423,7 +431,7 @@ static int rollout_launch(ssim_handle* h, int32_t kind, uint64_t seed, int32_t n
   hipLaunchKernelGGL(fn, dim3(L.num_envs), dim3(64),
                      (size_t)lds, (hipStream_t)stream,
                      dparams(h), h->state, h->obs, kind, seed, num_steps, flags, time_limits, h->reset, action_log,
-                     (uint64_t*)nullptr, budget, env_steps);
+                     prof_out, budget, env_steps);
   const int rc2 = hip_check(hipGetLastError(), "k_rollout launch");
   if (rc2 == SSIM_OK && budget > 0) h->ticket_slot ^= 1;
   return rc2;
@@ -468,39 +476,16 @@ extern "C" int ssim_reset_sampled(ssim_handle* h, const uint8_t* mode, const uin
 // Diagnostic build only: same rollout, per-wave phase cycle sums -> prof_out[num_envs][kNumPhases].
 extern "C" int ssim_rollout_profiled(ssim_handle* h, int32_t kind, uint64_t seed, int32_t num_steps,
                                      uint64_t* prof_out, void* stream) {
-  const ssim_layout& L = h->params.L;
-  const KernelSet ks = pick_kernels(h->params);
-  const RolloutFn fn = ks.rollout;
-  const int64_t lds = h->params.O.lds_bytes;
-  const int rc = lds_opt_in((const void*)fn, lds);
-  if (rc != SSIM_OK) return rc;
-  hipLaunchKernelGGL(fn, dim3(L.num_envs), dim3(64), (size_t)lds, (hipStream_t)stream,
-                     dparams(h), h->state, h->obs, kind, seed, num_steps, 0, (const double*)nullptr, h->reset,
-                     (int32_t*)nullptr, prof_out, (int64_t)0, (const int32_t*)nullptr);
-  return hip_check(hipGetLastError(), "k_rollout(profiled) launch");
+  return rollout_launch(h, kind, seed, num_steps, 0, 0, nullptr, nullptr, stream, nullptr, prof_out);
 }
 // Diagnostic build only: the budget rollout (as bench.py) with per-wave phase sums and realtime stamps.
 extern "C" int ssim_rollout_budget_profiled(ssim_handle* h, int32_t kind, uint64_t seed, int32_t max_steps,
                                             int64_t total_decisions, int32_t flags, uint64_t* prof_out,
                                             const double* time_limits, void* stream) {
-  const ssim_layout& L = h->params.L;
   if (total_decisions <= 0) return set_err(SSIM_E_ARG, "ssim_rollout_budget_profiled: total_decisions must be > 0");
-  const KernelSet ks = pick_kernels(h->params);
-  const RolloutFn fn = ks.rollout;
-  const int64_t lds = h->params.O.lds_bytes;
-  const int rc = lds_opt_in((const void*)fn, lds);
-  if (rc != SSIM_OK) return rc;
-  if (h->ticket_slot) flags |= kFlagTicketSlot;
-  hipLaunchKernelGGL(fn, dim3(L.num_envs), dim3(64), (size_t)lds, (hipStream_t)stream,
-                     dparams(h), h->state, h->obs, kind, seed, max_steps, flags, time_limits, h->reset,
-                     (int32_t*)nullptr, prof_out, total_decisions, (const int32_t*)nullptr);
-  const int rc2 = hip_check(hipGetLastError(), "k_rollout(budget, profiled) launch");
-  if (rc2 == SSIM_OK) h->ticket_slot ^= 1;
-  return rc2;
+  return rollout_launch(h, kind, seed, max_steps, total_decisions, flags, time_limits, nullptr, stream, nullptr,
+                        prof_out);
 }
-#endif
-
-#ifdef SSIM_PROFILE
 // Diagnostic build only: the next ssim_decima_rollout launch on `h` writes its per-wave phase sums to prof_out.
 extern "C" int ssim_decima_profile_next(ssim_handle* h, uint64_t* prof_out) {
   h->prof_next = prof_out;
@@ -522,31 +507,32 @@ extern "C" int ssim_job_times(ssim_handle* h, double* t_arrival, double* t_compl
   return hip_check(hipGetLastError(), "k_job_times launch");
 }
 
-// The set KAT (tests/test_gpu_sets.py) through the engine instantiation a launch on this handle runs: variant
-// SSIM_DEBUG_ENGINE the step / rollout kernels' (pick_kernels), SSIM_DEBUG_DECIMA the persistent Decima rollout's
-// (pick_decima), SSIM_DEBUG_KAT_BAD the test-only known-bad page assembly (N = 100 / J = 200, HBM-resident layouts).
+// The unit a launch on this handle runs, by its units.h name (null: the variant does not apply to the layout), and the
+// set KAT (tests/test_gpu_sets.py) through that unit's engine instantiation (`fn` null: a name only). SSIM_DEBUG_ENGINE:
+// the step / rollout kernels'; SSIM_DEBUG_DECIMA: the persistent Decima rollout's; SSIM_DEBUG_KAT_BAD: the test-only
+// known-bad page assembly (N = 100 / J = 200, HBM-resident layouts).
 static const char* debug_variant(const ssim_handle* h, int32_t variant, SetTraceFn* fn) {
-  if (variant == SSIM_DEBUG_ENGINE) {
-    const KernelSet k = pick_kernels(h->params);
-    *fn = k.set_trace;
-    return k.name;
-  }
-  if (variant == SSIM_DEBUG_DECIMA) {
-    const DecimaRolloutSet k = pick_decima(h->params);
-    *fn = k.set_trace;
-    return k.name;
-  }
-  if (variant == SSIM_DEBUG_KAT_BAD && large_shape(h->params) && !h->params.O.lds_resident) {
-    *fn = set_trace_kat_bad();
-    return "kat_bad_page";
-  }
+  const Params& p = h->params;
+  const DecimaUnit du = unit_of(p, decima_unit);
   *fn = nullptr;
+  switch (variant) {
+    case SSIM_DEBUG_ENGINE:
+      *fn = pick_kernels(p).set_trace;
+      return engine_unit_name(unit_of(p, engine_unit));
+    case SSIM_DEBUG_DECIMA:
+      *fn = pick_decima(p).set_trace;
+      return decima_unit_name(du);
+    case SSIM_DEBUG_DECIMA_GREEDY: return decima_unit_name(du, true);
+    case SSIM_DEBUG_PRIO: return prio_unit_name(unit_of(p, prio_unit));
+    case SSIM_DEBUG_KAT_BAD:
+      if (!shape_n100(p.L) || p.O.lds_resident) return nullptr;
+      *fn = set_trace_kat_bad();
+      return kKatBadName;
+  }
   return nullptr;
 }
 
 extern "C" const char* ssim_debug_kernel_name(const ssim_handle* h, int32_t variant) {
-  if (h != nullptr && variant == SSIM_DEBUG_DECIMA_GREEDY) return pick_decima_greedy(h->params).name;  // (a name only)
-  if (h != nullptr && variant == SSIM_DEBUG_PRIO) return prio_name(h->params);  // (a name only: no set KAT of its own)
   SetTraceFn fn;
   const char* n = h != nullptr ? debug_variant(h, variant, &fn) : nullptr;
   return n != nullptr ? n : "";
@@ -559,7 +545,7 @@ extern "C" int ssim_debug_set_trace_ex(ssim_handle* h, const int32_t* ops, int32
   if (h->params.L.num_executors > 127 || h->params.L.job_cap < 1)
     return set_err(SSIM_E_ARG, "ssim_debug_set_trace: needs 1..127 executors and a job cap >= 1");
   SetTraceFn fn = nullptr;
-  if (debug_variant(h, variant, &fn) == nullptr)
+  if (debug_variant(h, variant, &fn) == nullptr || fn == nullptr)
     return set_err(SSIM_E_ARG, "ssim_debug_set_trace: variant %d does not apply to this layout", variant);
   const int64_t lds = h->params.O.lds_bytes;
   const int rc = lds_opt_in((const void*)fn, lds);
@@ -655,12 +641,13 @@ struct DecimaLdsPlan {
   int32_t cap, off;
   int64_t lds;       // dynamic LDS of the launch
   int32_t help_off;  // the exec-score helpers' mailbox (units with helper waves), after the rest
+  int threads;       // block size: 64 per wave of the unit
 };
-static DecimaLdsPlan decima_lds_plan(const Params& P, const DecimaRolloutSet& ks) {
+static DecimaLdsPlan decima_lds_plan(const Params& P, int waves) {
   const StateOffsets& O = P.O;
   const ssim_layout& L = P.L;
-  DecimaLdsPlan pl{0, 0, O.lds_bytes, 0};
-  const int64_t help = ks.waves > 1 ? dp_help_bytes(L.num_executors) : 0;
+  DecimaLdsPlan pl{0, 0, O.lds_bytes, 0, 64 * waves};
+  const int64_t help = waves > 1 ? dp_help_bytes(L.num_executors) : 0;
   const int64_t eng = O.lds_resident ? O.hot_bytes + O.scratch_bytes : O.scratch_hbm_bytes;  // (HBM: row map cold)
   // Engines without the duration-descriptor cache hold only per-operation temporaries in their LDS scratch (set
   // tables, key lists, the commitment plan, observe()'s stage -> row map), none live across a decision: the plan
@@ -699,9 +686,20 @@ static DecimaLdsPlan decima_lds_plan(const Params& P, const DecimaRolloutSet& ks
   return pl;
 }
 
+// The launch shape of kernel `fn` of the unit row `k`, so that kernel, plan and block size are all of one row: the
+// row's LDS plan, into `a` too when given, and the opt-in for its dynamic LDS (a null `fn` only computes: no device call).
+static int decima_launch_plan(const ssim_handle* h, const DecimaUnitRow& k, const void* fn, DecimaRolloutArgs* a,
+                              DecimaLdsPlan* pl) {
+  *pl = decima_lds_plan(h->params, k.waves);
+  if (a != nullptr) a->plan_cap = pl->cap, a->plan_off = pl->off, a->help_off = pl->help_off;
+  return fn != nullptr ? lds_opt_in(fn, pl->lds) : SSIM_OK;
+}
+
 extern "C" int64_t ssim_decima_rollout_lds_bytes(const ssim_handle* h) {
   if (h == nullptr) return set_err(SSIM_E_ARG, "ssim_decima_rollout_lds_bytes: null handle");
-  return decima_lds_plan(h->params, pick_decima(h->params)).lds;
+  DecimaLdsPlan pl;
+  (void)decima_launch_plan(h, pick_decima(h->params), nullptr, nullptr, &pl);
+  return pl.lds;
 }
 
 // Test hook (host only, no launch): the node cap of the LDS plan and the waves per workgroup of the unit that
@@ -709,9 +707,10 @@ extern "C" int64_t ssim_decima_rollout_lds_bytes(const ssim_handle* h) {
 extern "C" int ssim_debug_decima_plan(const ssim_handle* h, int32_t* cap, int32_t* waves) {
   if (h == nullptr || cap == nullptr || waves == nullptr)
     return set_err(SSIM_E_ARG, "ssim_debug_decima_plan: null argument");
-  const DecimaRolloutSet ks = pick_decima(h->params);
-  *cap = decima_lds_plan(h->params, ks).cap;
-  *waves = ks.waves;
+  DecimaLdsPlan pl;
+  (void)decima_launch_plan(h, pick_decima(h->params), nullptr, nullptr, &pl);
+  *cap = pl.cap;
+  *waves = pl.threads / 64;
   return SSIM_OK;
 }
 
@@ -778,13 +777,11 @@ extern "C" int ssim_decima_rollout(ssim_handle* h, const float* params, int32_t 
       (flags & (SSIM_ROLLOUT_AUTORESET | SSIM_ROLLOUT_PREEMPT | SSIM_ROLLOUT_WARMUP | SSIM_ROLLOUT_TEST_REJECT)) != 0)
     return set_err(SSIM_E_ARG, "ssim_decima_rollout: SSIM_ROLLOUT_GREEDY does not combine with SSIM_ROLLOUT_AUTORESET / "
                    "PREEMPT / WARMUP / TEST_REJECT (flags 0x%x)", flags);
-  if ((flags & ~(SSIM_ROLLOUT_AUTORESET | SSIM_ROLLOUT_PREEMPT | SSIM_ROLLOUT_WARMUP | SSIM_ROLLOUT_TEST_REJECT |
-                 SSIM_ROLLOUT_GREEDY)) != 0)
-    return set_err(SSIM_E_ARG, "ssim_decima_rollout: unknown flags 0x%x", flags);
-  if ((flags & SSIM_ROLLOUT_PREEMPT) && total_decisions <= 0)
-    return set_err(SSIM_E_ARG, "ssim_decima_rollout: SSIM_ROLLOUT_PREEMPT needs a decision budget");
-  if ((flags & SSIM_ROLLOUT_AUTORESET) && !(h->params.C.job_arrival_gap > 0.0))
-    return set_err(SSIM_E_ARG, "ssim_decima_rollout: auto-reset needs job_arrival_gap in the config");
+  const int rc0 = check_rollout_flags("ssim_decima_rollout", h, flags,
+                                      SSIM_ROLLOUT_AUTORESET | SSIM_ROLLOUT_PREEMPT | SSIM_ROLLOUT_WARMUP |
+                                          SSIM_ROLLOUT_TEST_REJECT | SSIM_ROLLOUT_GREEDY,
+                                      total_decisions);
+  if (rc0 != SSIM_OK) return rc0;
   DecimaRolloutArgs a{};
   {
     const int rc = decima_rollout_args("ssim_decima_rollout", h, params, num_params, num_tasks_scale, work_scale, seed,
@@ -792,35 +789,20 @@ extern "C" int ssim_decima_rollout(ssim_handle* h, const float* params, int32_t 
     if (rc != SSIM_OK) return rc;
   }
   const ssim_layout& L = h->params.L;
-  const DecimaRolloutSet ks = pick_decima(h->params);
-  // (greedy: the plan caps and the waves are those of the sibling unit `ks`; the kernel never sees the flag's bit)
-  const DecimaRolloutFn fn = greedy                         ? pick_decima_greedy(h->params).rollout
-                             : (flags & SSIM_ROLLOUT_WARMUP) ? ks.rollout_warmup
-                                                             : ks.rollout;
-  flags &= ~SSIM_ROLLOUT_GREEDY;
-  const DecimaLdsPlan pl = decima_lds_plan(h->params, ks);
-  a.plan_cap = pl.cap;
-  a.plan_off = pl.off;
-  a.help_off = pl.help_off;
-  const int64_t lds = pl.lds;
-  const int rc = lds_opt_in((const void*)fn, lds);
+  const DecimaUnitRow& ks = pick_decima(h->params);
+  const DecimaRolloutFn fn = greedy ? ks.greedy : (flags & SSIM_ROLLOUT_WARMUP) ? ks.rollout_warmup : ks.rollout;
+  flags &= ~SSIM_ROLLOUT_GREEDY;  // (the kernel never sees the flag's bit)
+  DecimaLdsPlan ln;
+  const int rc = decima_launch_plan(h, ks, (const void*)fn, &a, &ln);
   if (rc != SSIM_OK) return rc;
   if (total_decisions > 0 && h->ticket_slot) flags |= kFlagTicketSlot;
-  hipLaunchKernelGGL(fn, dim3(L.num_envs), dim3(64 * ks.waves), (size_t)lds, (hipStream_t)stream, dparams(h),
+  hipLaunchKernelGGL(fn, dim3(L.num_envs), dim3(ln.threads), (size_t)ln.lds, (hipStream_t)stream, dparams(h),
                      h->state, h->obs, a, max_steps, flags, time_limits, h->reset, action_log, total_decisions,
                      h->prof_next);
   h->prof_next = nullptr;
   const int rc2 = hip_check(hipGetLastError(), "k_decima_rollout launch");
   if (rc2 == SSIM_OK && total_decisions > 0) h->ticket_slot ^= 1;
   return rc2;
-}
-
-// The fixed-duration kernel of the unit pick_decima selects (same layout rule, same LDS plan, same waves).
-static DecimaTimedFn pick_decima_timed(const Params& p) {
-  return p.O.lds_resident                        ? (decima_shape(p) && !generic_forced() ? decima_timed_lds50()
-                                                                                        : decima_timed_lds())
-         : !decima_shape(p) || generic_forced() ? decima_timed_hbm()
-                                                : decima_timed_hbm50();
 }
 
 extern "C" int ssim_decima_rollout_timed(ssim_handle* h, const float* params, int32_t num_params,
@@ -856,15 +838,12 @@ extern "C" int ssim_decima_rollout_timed(ssim_handle* h, const float* params, in
                                        seed, counter, workspace, workspace_bytes, samples, stream, &a);
     if (rc != SSIM_OK) return rc;
   }
-  const DecimaRolloutSet ks = pick_decima(h->params);  // (the plan and the waves of the timed kernel's sibling unit)
-  const DecimaTimedFn fn = pick_decima_timed(h->params);
-  const DecimaLdsPlan pl = decima_lds_plan(h->params, ks);
-  a.plan_cap = pl.cap;
-  a.plan_off = pl.off;
-  a.help_off = pl.help_off;
-  const int rc = lds_opt_in((const void*)fn, pl.lds);
+  const DecimaUnitRow& ks = pick_decima(h->params);
+  const DecimaTimedFn fn = ks.timed;
+  DecimaLdsPlan ln;
+  const int rc = decima_launch_plan(h, ks, (const void*)fn, &a, &ln);
   if (rc != SSIM_OK) return rc;
-  hipLaunchKernelGGL(fn, dim3(h->params.L.num_envs), dim3(64 * ks.waves), (size_t)pl.lds, (hipStream_t)stream,
+  hipLaunchKernelGGL(fn, dim3(h->params.L.num_envs), dim3(ln.threads), (size_t)ln.lds, (hipStream_t)stream,
                      dparams(h), h->state, h->obs, a, t, max_steps, flags, h->reset, action_log, h->prof_next);
   h->prof_next = nullptr;
   return hip_check(hipGetLastError(), "k_decima_rollout_timed launch");

@@ -184,6 +184,11 @@ class _ResetSampler:
         return len(tpl)
 
 
+def _ptr(x):
+    """Device address of an optional tensor."""
+    return None if x is None else x.data_ptr()
+
+
 class DeviceEngine:
     """B independent envs on one GPU. All tensors live on `device`; nothing is copied per step."""
 
@@ -242,6 +247,15 @@ class DeviceEngine:
     def _stream(self):
         return ct.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
 
+    def _limits(self, time_limits):
+        """Per-env time limits as a float64 device tensor [num_envs] (a tensor is used in place), or None."""
+        t = self.torch
+        if time_limits is None:
+            return None
+        if isinstance(time_limits, t.Tensor):
+            return time_limits.to(device=self.device, dtype=t.float64).contiguous()
+        return t.as_tensor(np.asarray(time_limits, dtype=np.float64).reshape(self.num_envs), device=self.device)
+
     def _rng_words(self, env: int):
         off = PARAMS_RESERVE + env * self.layout.env_bytes + HEADER_RNG_OFFSET
         raw = self.state[off: off + 40].cpu().numpy()
@@ -296,42 +310,26 @@ class DeviceEngine:
             sd = seeds.to(device=self.device, dtype=t.int64).contiguous()
         elif seeds is not None:
             sd = t.as_tensor(np.asarray(seeds, dtype=np.uint64).view(np.int64).reshape(B), device=self.device)
-        tl = None
-        if isinstance(time_limits, t.Tensor):
-            tl = time_limits.to(device=self.device, dtype=t.float64).contiguous()
-        elif time_limits is not None:
-            tl = t.as_tensor(np.asarray(time_limits, dtype=np.float64).reshape(B), device=self.device)
+        tl = self._limits(time_limits)
         self._keep = (m, sd, tl)
-        self._native.check(self._native.lib().ssim_reset_sampled(
-            self.handle, m.data_ptr(), None if sd is None else sd.data_ptr(), None if tl is None else tl.data_ptr(),
-            self._stream()), "ssim_reset_sampled")
+        self._native.check(self._native.lib().ssim_reset_sampled(self.handle, m.data_ptr(), _ptr(sd), _ptr(tl),
+                                                                 self._stream()), "ssim_reset_sampled")
 
     def rollout(self, kind: int, seed: int, num_steps: int, action_log=None, flags: int = 0, time_limits=None):
         """`num_steps` fused policy+step launches' worth of decisions in ONE kernel launch. flags:
         _abi.SSIM_ROLLOUT_AUTORESET resets finished episodes in place (limits from `time_limits`)."""
-        ptr = action_log.data_ptr() if action_log is not None else None
-        tl = None
-        if time_limits is not None:
-            tl = self.torch.as_tensor(np.asarray(time_limits, dtype=np.float64).reshape(self.num_envs),
-                                      device=self.device) if not hasattr(time_limits, "data_ptr") else time_limits
-        self._keep_tl = tl
+        self._keep_tl = tl = self._limits(time_limits)
         self._native.check(self._native.lib().ssim_rollout_ex(
-            self.handle, kind, seed, num_steps, flags, None if tl is None else tl.data_ptr(), ptr, self._stream()),
-            "ssim_rollout")
+            self.handle, kind, seed, num_steps, flags, _ptr(tl), _ptr(action_log), self._stream()), "ssim_rollout")
 
     def rollout_budget(self, kind: int, seed: int, max_steps: int, total_decisions: int, action_log=None,
                        flags: int = 0, time_limits=None):
         """Work-conserving rollout (ssim_rollout_budget): `total_decisions` decisions shared by all envs, each
         env at most `max_steps`; each env's decisions equal those of `rollout`, only their number differs."""
-        ptr = action_log.data_ptr() if action_log is not None else None
-        tl = None
-        if time_limits is not None:
-            tl = self.torch.as_tensor(np.asarray(time_limits, dtype=np.float64).reshape(self.num_envs),
-                                      device=self.device) if not hasattr(time_limits, "data_ptr") else time_limits
-        self._keep_tl = tl
+        self._keep_tl = tl = self._limits(time_limits)
         self._native.check(self._native.lib().ssim_rollout_budget(
-            self.handle, kind, seed, max_steps, total_decisions, flags, None if tl is None else tl.data_ptr(), ptr,
-            self._stream()), "ssim_rollout_budget")
+            self.handle, kind, seed, max_steps, total_decisions, flags, _ptr(tl), _ptr(action_log), self._stream()),
+            "ssim_rollout_budget")
 
     def rollout_steps(self, kind: int, seed: int, env_steps, max_steps: int, action_log=None, flags: int = 0,
                       time_limits=None):
@@ -340,15 +338,11 @@ class DeviceEngine:
         t = self.torch
         st = t.as_tensor(np.asarray(env_steps, dtype=np.int32).reshape(self.num_envs), device=self.device) \
             if not isinstance(env_steps, t.Tensor) else env_steps.to(device=self.device, dtype=t.int32).contiguous()
-        ptr = action_log.data_ptr() if action_log is not None else None
-        tl = None
-        if time_limits is not None:
-            tl = t.as_tensor(np.asarray(time_limits, dtype=np.float64).reshape(self.num_envs),
-                             device=self.device) if not hasattr(time_limits, "data_ptr") else time_limits
+        tl = self._limits(time_limits)
         self._keep_tl = (st, tl)
         self._native.check(self._native.lib().ssim_rollout_steps(
-            self.handle, kind, seed, st.data_ptr(), max_steps, flags, None if tl is None else tl.data_ptr(), ptr,
-            self._stream()), "ssim_rollout_steps")
+            self.handle, kind, seed, st.data_ptr(), max_steps, flags, _ptr(tl), _ptr(action_log), self._stream()),
+            "ssim_rollout_steps")
 
     def host_views(self) -> dict:
         return arena_views(self.obs.cpu().numpy(), self.layout)
@@ -401,6 +395,18 @@ class DeviceEngine:
             self._dws = self.torch.zeros(n, dtype=self.torch.uint8, device=self.device)
         return self._dws
 
+    def _decima_args(self, params, seed, counter, max_steps, total_decisions, flags, time_limits, samples,
+                     num_tasks_scale, work_scale, *keep):
+        """The arguments ssim_decima_rollout and ssim_decima_rollout_timed share, up to the sample arena; what they
+        point to is kept alive with the launch (`keep`: the caller's own)."""
+        ws = self.decima_workspace()
+        tl = self._limits(time_limits)
+        st = samples.struct() if samples is not None else None
+        self._keep_dr = (params, tl, st, *keep)
+        return (self.handle, params.data_ptr(), params.numel(), float(num_tasks_scale), float(work_scale),
+                int(seed) & (2**64 - 1), int(counter) & (2**64 - 1), int(max_steps), int(total_decisions), int(flags),
+                _ptr(tl), ws.data_ptr(), ws.numel(), None if st is None else ct.byref(st))
+
     def decima_rollout(self, params, seed: int, counter: int, max_steps: int, total_decisions: int = 0,
                        flags: int = 0, time_limits=None, samples=None, action_log=None,
                        num_tasks_scale: float = 200.0, work_scale: float = 1e5):
@@ -409,19 +415,10 @@ class DeviceEngine:
         flags: 0 = collect until each env's episode ends; _abi.SSIM_ROLLOUT_AUTORESET / PREEMPT (with
         total_decisions) / WARMUP as ssim_rollout_budget; _abi.SSIM_ROLLOUT_GREEDY (with none of those) takes the
         policy's arg-max action at every decision (seed / counter unused)."""
-        ws = self.decima_workspace()
-        tl = None
-        if time_limits is not None:
-            tl = self.torch.as_tensor(np.asarray(time_limits, dtype=np.float64).reshape(self.num_envs),
-                                      device=self.device) if not hasattr(time_limits, "data_ptr") else time_limits
-        st = samples.struct() if samples is not None else None
-        self._keep_dr = (params, tl, st)
-        self._native.check(self._native.lib().ssim_decima_rollout(
-            self.handle, params.data_ptr(), params.numel(), float(num_tasks_scale), float(work_scale),
-            int(seed) & (2**64 - 1), int(counter) & (2**64 - 1), int(max_steps), int(total_decisions), int(flags),
-            None if tl is None else tl.data_ptr(), ws.data_ptr(), ws.numel(),
-            None if st is None else ct.byref(st), None if action_log is None else action_log.data_ptr(),
-            self._stream()), "ssim_decima_rollout")
+        args = self._decima_args(params, seed, counter, max_steps, total_decisions, flags, time_limits, samples,
+                                 num_tasks_scale, work_scale)
+        self._native.check(self._native.lib().ssim_decima_rollout(*args, _ptr(action_log), self._stream()),
+                           "ssim_decima_rollout")
 
     def decima_rollout_timed(self, params, seed: int, counter: int, max_steps: int, samples, timed,
                              flags: int = 0, total_decisions: int = 0, time_limits=None, action_log=None,
@@ -431,19 +428,11 @@ class DeviceEngine:
         the library; None is passed through so its refusal can be tested); timed: an _abi.SsimDecimaTimed whose
         device arrays are `tensors` (kept alive with the launch, as `params` is). flags / total_decisions /
         time_limits exist to be refused: the mode combines with none of them."""
-        ws = self.decima_workspace()
-        tl = None
-        if time_limits is not None:
-            tl = self.torch.as_tensor(np.asarray(time_limits, dtype=np.float64).reshape(self.num_envs),
-                                      device=self.device) if not hasattr(time_limits, "data_ptr") else time_limits
-        st = samples.struct() if samples is not None else None
-        self._keep_dr = (params, tl, st, timed, tuple(tensors))
+        args = self._decima_args(params, seed, counter, max_steps, total_decisions, flags, time_limits, samples,
+                                 num_tasks_scale, work_scale, timed, tuple(tensors))
         self._native.check(self._native.lib().ssim_decima_rollout_timed(
-            self.handle, params.data_ptr(), params.numel(), float(num_tasks_scale), float(work_scale),
-            int(seed) & (2**64 - 1), int(counter) & (2**64 - 1), int(max_steps), int(total_decisions), int(flags),
-            None if tl is None else tl.data_ptr(), ws.data_ptr(), ws.numel(),
-            None if st is None else ct.byref(st), None if timed is None else ct.byref(timed),
-            None if action_log is None else action_log.data_ptr(), self._stream()), "ssim_decima_rollout_timed")
+            *args, None if timed is None else ct.byref(timed), _ptr(action_log), self._stream()),
+            "ssim_decima_rollout_timed")
 
     def decima_features_np(self,num_tasks_scale: float = 200.0, work_scale: float = 1e5) -> dict:
         return {k: x.cpu().numpy() for k, x in self.decima_features(num_tasks_scale, work_scale).items()}

@@ -18,6 +18,48 @@ class NativeError(RuntimeError):
     pass
 
 
+_vp, _i32, _i64, _u64, _f32 = ct.c_void_p, ct.c_int32, ct.c_int64, ct.c_uint64, ct.c_float
+_DECIMA_ROLLOUT = [_vp, _vp, _i32, _f32, _f32, _u64, _u64, _i32, _i64, _i32, _vp, _vp, _i64, _vp]
+# The C ABI (include/sparksched.h): (symbol, restype, argtypes). lib() sets every prototype from this one table.
+_PROTOTYPES = [
+    ("ssim_layout_for", ct.c_int, [ct.POINTER(SsimConfig), ct.POINTER(SsimLayout)]),
+    ("ssim_create", ct.c_int, [ct.POINTER(SsimConfig), ct.POINTER(SsimDataset), _vp, _vp, _vp, ct.POINTER(_vp)]),
+    ("ssim_destroy", ct.c_int, [_vp]),
+    ("ssim_reset", ct.c_int, [_vp, _vp]),
+    ("ssim_step", ct.c_int, [_vp, _vp, _vp, _vp]),
+    ("ssim_policy", ct.c_int, [_vp, _i32, _u64, _u64, _vp, _vp, _vp]),
+    ("ssim_rollout", ct.c_int, [_vp, _i32, _u64, _i32, _vp, _vp]),
+    ("ssim_rollout_ex", ct.c_int, [_vp, _i32, _u64, _i32, _i32, _vp, _vp, _vp]),
+    ("ssim_rollout_budget", ct.c_int, [_vp, _i32, _u64, _i32, _i64, _i32, _vp, _vp, _vp]),
+    ("ssim_rollout_steps", ct.c_int, [_vp, _i32, _u64, _vp, _i32, _i32, _vp, _vp, _vp]),
+    ("ssim_reset_sampled", ct.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    ("ssim_job_times", ct.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    ("ssim_episode_stats", ct.c_int, [_vp, _vp, _vp]),
+    ("ssim_decima_features", ct.c_int, [_vp, _f32, _f32, _vp, _vp, _vp, _vp, _vp]),
+    ("ssim_decima_policy", ct.c_int, [_vp] * 6 + [_i32, _i32, _u64, _u64] + [_vp] * 10),
+    ("ssim_decima_workspace_bytes", _i64, [_vp]),
+    ("ssim_decima_rollout", ct.c_int, _DECIMA_ROLLOUT + [_vp, _vp]),
+    ("ssim_decima_rollout_timed", ct.c_int, _DECIMA_ROLLOUT + [_vp, _vp, _vp]),
+    ("ssim_decima_rollout_lds_bytes", _i64, [_vp]),
+    ("ssim_debug_decima_plan", ct.c_int, [_vp, ct.POINTER(_i32), ct.POINTER(_i32)]),
+    ("ssim_last_error", ct.c_char_p, []),
+    ("ssim_build_id", ct.c_char_p, []),
+    ("ssim_debug_set_trace", ct.c_int, [_vp, _vp, _i32, _i32, _vp, _vp]),
+    ("ssim_debug_set_trace_ex", ct.c_int, [_vp, _vp, _i32, _i32, _vp, _i32, _vp]),
+    ("ssim_debug_kernel_name", ct.c_char_p, [_vp, _i32]),
+    ("ssim_linear_fwd", ct.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp]),
+    ("ssim_linear_wgrad_parts", _i32, [_i64]),
+    ("ssim_linear_wgrad", ct.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _i32, _vp]),
+    ("ssim_mlp3_supported", _i32, [_i32] * 5),
+    ("ssim_mlp3_fwd", ct.c_int, [_vp, _vp, _i32] + [_vp] * 9 + [_i64] + [_i32] * 5 + [_f32, _vp]),
+    ("ssim_mlp3_parts", _i32, [_i64]),
+    ("ssim_mlp3_partial_floats", _i64, [_i64, _i32, _i32, _i32, _i32]),
+    ("ssim_mlp3_bwd", ct.c_int, [_vp, _vp, _vp, _i32] + [_vp] * 14 + [_i64] + [_i32] * 5 + [_f32, _vp, _i32, _vp]),
+    ("ssim_discounted_returns", ct.c_int, [_vp, _vp, _vp, _i64, _i64, _i32, _vp]),
+]
+EXPORTED_SYMBOLS = [name for name, _, _ in _PROTOTYPES]
+
+
 def lib() -> ct.CDLL:
     global _lib
     if _lib is not None:
@@ -31,65 +73,9 @@ def lib() -> ct.CDLL:
             f"libsparksched.so not found at {LIB_PATH}; build it with `python __graft_entry__.py build` "
             "(hipcc --offload-arch=gfx950). The simulator has no CPU fallback.")
     L = ct.CDLL(LIB_PATH)
-    vp, i32, u64 = ct.c_void_p, ct.c_int32, ct.c_uint64
-    L.ssim_layout_for.argtypes = [ct.POINTER(SsimConfig), ct.POINTER(SsimLayout)]
-    L.ssim_create.argtypes = [ct.POINTER(SsimConfig), ct.POINTER(SsimDataset), vp, vp, vp, ct.POINTER(vp)]
-    L.ssim_destroy.argtypes = [vp]
-    L.ssim_reset.argtypes = [vp, vp]
-    L.ssim_step.argtypes = [vp, vp, vp, vp]
-    L.ssim_policy.argtypes = [vp, i32, u64, u64, vp, vp, vp]
-    L.ssim_rollout.argtypes = [vp, i32, u64, i32, vp, vp]
-    L.ssim_rollout_ex.argtypes = [vp, i32, u64, i32, i32, vp, vp, vp]
-    L.ssim_rollout_budget.argtypes = [vp, i32, u64, i32, ct.c_int64, i32, vp, vp, vp]
-    L.ssim_rollout_steps.argtypes = [vp, i32, u64, vp, i32, i32, vp, vp, vp]
-    L.ssim_reset_sampled.argtypes = [vp, vp, vp, vp, vp]
-    L.ssim_decima_policy.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, u64, u64, vp, vp, vp, vp, vp, vp, vp, vp, vp,
-                                     vp]
-    L.ssim_job_times.argtypes = [vp, vp, vp, vp, vp]
-    L.ssim_episode_stats.argtypes = [vp, vp, vp]
-    L.ssim_decima_features.argtypes = [vp, ct.c_float, ct.c_float, vp, vp, vp, vp, vp]
-    L.ssim_decima_workspace_bytes.argtypes = [vp]
-    L.ssim_decima_workspace_bytes.restype = ct.c_int64
-    L.ssim_decima_rollout_lds_bytes.argtypes = [vp]
-    L.ssim_decima_rollout_lds_bytes.restype = ct.c_int64
-    L.ssim_debug_decima_plan.argtypes = [vp, ct.POINTER(i32), ct.POINTER(i32)]
-    L.ssim_debug_decima_plan.restype = ct.c_int
-    L.ssim_decima_rollout.argtypes = [vp, vp, i32, ct.c_float, ct.c_float, u64, u64, i32, ct.c_int64, i32, vp, vp,
-                                      ct.c_int64, vp, vp, vp]
-    L.ssim_decima_rollout_timed.argtypes = [vp, vp, i32, ct.c_float, ct.c_float, u64, u64, i32, ct.c_int64, i32, vp,
-                                            vp, ct.c_int64, vp, vp, vp, vp]
-    L.ssim_last_error.restype = ct.c_char_p
-    L.ssim_build_id.restype = ct.c_char_p
-    L.ssim_debug_set_trace.argtypes = [vp, vp, i32, i32, vp, vp]
-    L.ssim_debug_set_trace.restype = ct.c_int
-    L.ssim_debug_set_trace_ex.argtypes = [vp, vp, i32, i32, vp, i32, vp]
-    L.ssim_debug_set_trace_ex.restype = ct.c_int
-    L.ssim_debug_kernel_name.argtypes = [vp, i32]
-    L.ssim_debug_kernel_name.restype = ct.c_char_p
-    L.ssim_linear_fwd.argtypes = [vp, vp, vp, vp, ct.c_int64, i32, i32, i32, vp]
-    L.ssim_linear_fwd.restype = ct.c_int
-    L.ssim_linear_wgrad_parts.argtypes = [ct.c_int64]
-    L.ssim_linear_wgrad_parts.restype = i32
-    L.ssim_linear_wgrad.argtypes = [vp, vp, vp, vp, ct.c_int64, i32, i32, vp, i32, vp]
-    L.ssim_linear_wgrad.restype = ct.c_int
-    L.ssim_mlp3_supported.argtypes = [i32, i32, i32, i32, i32]
-    L.ssim_mlp3_supported.restype = i32
-    L.ssim_mlp3_fwd.argtypes = [vp, vp, i32] + [vp] * 9 + [ct.c_int64, i32, i32, i32, i32, i32, ct.c_float, vp]
-    L.ssim_mlp3_fwd.restype = ct.c_int
-    L.ssim_mlp3_parts.argtypes = [ct.c_int64]
-    L.ssim_mlp3_parts.restype = i32
-    L.ssim_mlp3_partial_floats.argtypes = [ct.c_int64, i32, i32, i32, i32]
-    L.ssim_mlp3_partial_floats.restype = ct.c_int64
-    L.ssim_mlp3_bwd.argtypes = [vp, vp, vp, i32] + [vp] * 14 + [ct.c_int64, i32, i32, i32, i32, i32, ct.c_float, vp,
-                                                                 i32, vp]
-    L.ssim_mlp3_bwd.restype = ct.c_int
-    L.ssim_discounted_returns.argtypes = [vp, vp, vp, ct.c_int64, ct.c_int64, i32, vp]
-    L.ssim_discounted_returns.restype = ct.c_int
-    for name in ("ssim_layout_for", "ssim_create", "ssim_destroy", "ssim_reset", "ssim_step", "ssim_policy",
-                 "ssim_rollout", "ssim_rollout_ex", "ssim_rollout_budget", "ssim_rollout_steps", "ssim_reset_sampled",
-                 "ssim_job_times", "ssim_episode_stats", "ssim_decima_features", "ssim_decima_policy", "ssim_decima_rollout",
-                 "ssim_decima_rollout_timed"):
-        getattr(L, name).restype = ct.c_int
+    for name, restype, argtypes in _PROTOTYPES:
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = L
     return L
 
@@ -97,17 +83,6 @@ def lib() -> ct.CDLL:
 def check(rc: int, what: str) -> None:
     if rc != 0:
         raise NativeError(f"{what} failed ({rc}): {lib().ssim_last_error().decode(errors='replace')}")
-
-
-EXPORTED_SYMBOLS = ["ssim_layout_for", "ssim_create", "ssim_destroy", "ssim_reset", "ssim_step", "ssim_policy",
-                    "ssim_rollout", "ssim_rollout_ex", "ssim_rollout_budget", "ssim_rollout_steps", "ssim_reset_sampled",
-                    "ssim_job_times", "ssim_episode_stats",
-                    "ssim_decima_features", "ssim_decima_policy", "ssim_decima_workspace_bytes", "ssim_decima_rollout",
-                    "ssim_decima_rollout_timed", "ssim_decima_rollout_lds_bytes", "ssim_debug_decima_plan",
-                    "ssim_last_error", "ssim_build_id", "ssim_debug_set_trace", "ssim_debug_set_trace_ex",
-                    "ssim_debug_kernel_name", "ssim_linear_fwd",
-                    "ssim_linear_wgrad_parts", "ssim_linear_wgrad", "ssim_mlp3_supported", "ssim_mlp3_fwd",
-                    "ssim_mlp3_parts", "ssim_mlp3_partial_floats", "ssim_mlp3_bwd", "ssim_discounted_returns"]
 
 
 def build_id() -> str:

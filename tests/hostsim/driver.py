@@ -24,7 +24,7 @@ SO_PATH = os.environ.get("HOSTSIM_SO") or os.path.join(HERE, "_hostsim.so")
 ENV_FLAGS = os.environ.get("HOSTSIM_FLAGS", "").split()
 SOURCES = [os.path.join(HERE, "hostsim.cpp")] + [
     os.path.join(REPO, "gym-sparksched_amd", "csrc", f) for f in ("engine.h", "policy.h", "pyset.h", "pcg64.h", "decima.h", "fdlibm.h", "ziggurat.h",
-                                                                  "layout.h", "rollout.h")] + [
+                                                                  "layout.h", "rollout.h", "units.h")] + [
     os.path.join(REPO, "include", "sparksched.h")]
 
 _lib = None
@@ -79,6 +79,9 @@ def lib():
         L.hs_seed_words.argtypes = [ct.c_uint64, vp]
         L.hs_std_exponential.argtypes = [vp, ct.c_int, vp]
         L.hs_log1p.argtypes = [vp, ct.c_int, vp]
+        L.hs_unit_names.argtypes = [ct.POINTER(SsimLayout), ct.c_int, ct.c_int] + [ct.POINTER(ct.c_char_p)] * 4 + [
+            ct.POINTER(ct.c_int)]
+        L.hs_unit_names.restype = None
         _lib = L
     return _lib
 

@@ -40,6 +40,7 @@ static int64_t g_field[16];
 #include "engine.h"
 #include "policy.h"
 #include "rollout.h"
+#include "units.h"
 
 using namespace ssim;
 
@@ -401,6 +402,18 @@ int hs_pyset_trace(const int32_t* ops, int n_ops, int width, int32_t* orders) {
   free(tab);
   free(tab2);
   return 0;
+}
+
+// The C ABI's kernel-unit rule (units.h): the unit names and the Decima unit's waves per workgroup for a layout.
+void hs_unit_names(const ssim_layout* L, int lds_resident, int generic, const char** engine, const char** decima,
+                   const char** greedy, const char** prio, int* waves) {
+  const bool res = lds_resident != 0, gen = generic != 0;
+  const DecimaUnit d = decima_unit(*L, res, gen);
+  *engine = engine_unit_name(engine_unit(*L, res, gen));
+  *decima = decima_unit_name(d);
+  *greedy = decima_unit_name(d, true);
+  *prio = prio_unit_name(prio_unit(*L, res, gen));
+  *waves = decima_unit_waves(d);
 }
 
 }  // extern "C"
