@@ -111,6 +111,18 @@ class RolloutCollector:
         """rollout_worker.py:122-129 per row, float64 [B, 4] on the policy's device (metrics.RowStats)."""
         return torch.from_numpy(self.stats.stats(self.engine)).to(self.policy.device)
 
+    def _stream_counter(self, base: int) -> int:
+        # the kernel hashes (local env * C + counter); adding row_offset * C to the counter makes that the
+        # hash of the global row (C: the constant below, csrc/decima_policy.h decima_policy_env)
+        return (base + self.row_offset * 0x9E3779B97F4A7C15) & (2**64 - 1)
+
+    def _check_not_frozen(self) -> None:
+        err = self.engine.views["counts"][:, _abi.OC_ERR].cpu().numpy() & _abi.SSIM_ERR_STICKY
+        if err.any():  # e.g. an action the engine refused (frozen with SSIM_ERR_INVARIANT): its samples are invalid
+            bad = np.flatnonzero(err)
+            raise RuntimeError(f"decima rollout: envs {bad[:8].tolist()} frozen with error bits "
+                               f"{[hex(int(x)) for x in err[bad[:8]]]}")
+
     def _views(self, features: bool = True):
         eng = self.engine
         if self.on_device:
@@ -144,11 +156,8 @@ class RolloutCollector:
             self.counter += 1
             if self._params is None:  # weights are fixed for a whole collect(): pack them once
                 self._params = self.policy.packed_params(eng.device)
-            # the kernel hashes (local env * C + counter); adding row_offset * C to the counter makes that the
-            # hash of the global row (C = 0x9E3779B97F4A7C15, csrc/decima_policy.h decima_policy_env)
-            ctr = (self.counter + self.row_offset * 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF
-            fo = self.policy.schedule_fused(eng, f, seed=self.seed, counter=ctr, env_mask=alive,
-                                            node_cap=batch.max_nodes, params=self._params)
+            fo = self.policy.schedule_fused(eng, f, seed=self.seed, counter=self._stream_counter(self.counter),
+                                            env_mask=alive, node_cap=batch.max_nodes, params=self._params)
             act = {"stage_idx": fo["stage_idx"], "num_exec": fo["num_exec"], "job_idx": fo["job_idx"].long(),
                    "exec_idx": fo["exec_idx"].long(), "lgprob": fo["lgprob"]}
         else:
@@ -377,7 +386,7 @@ class DeviceRolloutCollector(RolloutCollector):
         self.stats.flush(range(B), eng)
         eng.reset_sampled(_abi.SSIM_RESET_SEED, seeds=seeds, time_limits=limits)
         params = self.policy.packed_params(eng.device)
-        ctr = ((self.calls << 32) + 1 + self.row_offset * 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF
+        ctr = self._stream_counter((self.calls << 32) + 1)
         self.arena.clear()
         steps = int(min(max_steps, 2**31 - 1))
         while True:
@@ -388,11 +397,7 @@ class DeviceRolloutCollector(RolloutCollector):
             if not (cur[:, _abi.CUR_FULL] != 0).any():
                 break
             self.arena.grow(cur)
-        err = eng.views["counts"][:, _abi.OC_ERR].cpu().numpy() & _abi.SSIM_ERR_STICKY
-        if err.any():  # e.g. an action the engine refused (frozen with SSIM_ERR_INVARIANT): its samples are invalid
-            bad = np.flatnonzero(err)
-            raise RuntimeError(f"decima rollout: envs {bad[:8].tolist()} frozen with error bits "
-                               f"{[hex(int(x)) for x in err[bad[:8]]]}")
+        self._check_not_frozen()
         wall = eng.views["wall_time"].double().clone()
         return self.arena.buffer(wall)
 
@@ -580,7 +585,7 @@ class DeviceAsyncRolloutCollector(AsyncRolloutCollector):
         if self.next_wall is None:  # first call: reset every worker on the host path (reset 0 of every row)
             self._reset(np.arange(eng.num_envs))
         params = self.policy.packed_params(eng.device)
-        ctr = ((self.calls << 32) + 1 + self.row_offset * 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF
+        ctr = self._stream_counter((self.calls << 32) + 1)
         self.arena.clear()
         self.clock.zero_()
         seeds, limits = self._fill_schedule()
@@ -609,11 +614,7 @@ class DeviceAsyncRolloutCollector(AsyncRolloutCollector):
                 self.refills += 1
             if used.any():  # the next launch's slots continue each row's seed stream
                 seeds, limits = self._fill_schedule()
-        err = eng.views["counts"][:, _abi.OC_ERR].cpu().numpy() & _abi.SSIM_ERR_STICKY
-        if err.any():  # e.g. an action the engine refused (frozen with SSIM_ERR_INVARIANT): its samples are invalid
-            bad = np.flatnonzero(err)
-            raise RuntimeError(f"decima rollout: envs {bad[:8].tolist()} frozen with error bits "
-                               f"{[hex(int(x)) for x in err[bad[:8]]]}")
+        self._check_not_frozen()
         self.next_wall = eng.views["wall_time"].double().clone()
         buf = self.arena.buffer(self.clock[:, 0].clone())  # times are elapsed times: the final one closes each row
         buf.resets = sorted(resets, key=lambda r: (r[1], r[0]))  # (env, step) in the lockstep loop's order

@@ -1,17 +1,34 @@
 """TEST INFRASTRUCTURE ONLY — audits a filled sample arena of the persistent Decima rollout (ssim_decima_rollout,
-csrc/decima_rollout.h) against the CPU oracle: the env (oracle/restatement.py), the Decima observation wrapper
-(oracle/decima.py), the per-observation fp32 GNN policy (oracle/decima_gnn.py) and a numpy restatement of the device
-sampling stream (csrc/policy.h splitmix64, csrc/decima_policy.h dp_gumbel).
+csrc/decima_rollout.h), sampled or greedy (SSIM_ROLLOUT_GREEDY, csrc/decima_policy.h kGreedy), against the CPU oracle:
+the env (oracle/restatement.py), the Decima observation wrapper (oracle/decima.py), the per-observation fp32 GNN policy
+(oracle/decima_gnn.py) and a numpy restatement of the device sampling stream (csrc/policy.h splitmix64,
+csrc/decima_policy.h dp_gumbel).
 
 The replay tests show the engine is right GIVEN the rollout's actions; this module checks what the rollout computed
-to choose them: every recorded observation row, the log-probability and the Gumbel-max draw of the recorded action.
+to choose them. ONE walk (_walk_env) drives the oracle through an arena's samples and checks every recorded
+observation row, wall time, reward, the record's consistency and the log-probability of the recorded action; a CHOICE
+RULE supplies only what differs between the two kinds of rollout:
+
+  Sampled  the oracle's scores plus the device stream's Gumbel noise; the Gumbel-max winner must be the recorded choice
+           wherever it leads the runner-up by more than the score margin, draws inside the margin are SKIPPED and
+           counted (more than MAX_SKIP_SHARE of them fails); the policy checks run on every `every`-th sample.
+  Greedy   no noise, and REGRET instead of skipping: with the noise at zero the skipping rule skips too much (2.7-3.3%
+           of an untrained policy's decisions lie inside the margin, up to 96% once the tanh layers saturate). Every
+           recorded choice must be numerically indistinguishable from the best: ss[stage_idx] >= max(ss) - s_margin and
+           es[exec_idx] >= max(es) - e_margin, on every sample. Where the oracle's winner leads by more than the margin
+           this forces the recorded choice to be the winner; elsewhere it accepts only choices within the margin of the
+           best. A decision is DECISIVE when both leads exceed their margins.
+
+The margins are 2 (SCORE_ATOL + SCORE_RTOL max|score|), per score vector.
 
   gumbel_np           the device's Gumbel noise for (seed, env, counter, item), stage or exec draw
   host_arena          numpy copies of a DecimaSampleArena (any device)
   sample_observation  the reference-format Decima observation of one recorded sample
+  policy              the oracle's scores of one observation, winners (arg-max, first maximal index), leads and margins
   audit               the checks, per env; raises parity.Mismatch, returns per-sample sizes and path classes
   reference_rollout   the same walk with the reference's own winners as actions (what a correct kernel records)
   collect_reference   a sample arena filled on the host build of the engine, actions from the oracle policy
+Helpers of the tests that use the auditor: policy_state, replanned, gpu_collect, arenas_equal.
 """
 
 from __future__ import annotations
@@ -144,37 +161,120 @@ def classify(dobs: dict, job_idx: int, num_executors: int, plan_cap: int, helper
     return plan, "many" if int(caps[job_idx]) > TILE else "single"
 
 
-# ------------------------------------------------------------------------------------------ the walk
-def _policy(sd: dict, dobs: dict, num_executors: int, seed: int, env: int, ctr: int, stage_of=None,
-            stage_key_exec: bool = False):
-    """The oracle policy on one observation and the device stream's draws: stage scores, their Gumbel-max winner and
-    its lead over the runner-up; then, for the DAG of stage `stage_of` (default: the winner), the same for the exec
-    scores. Scores are float32 (the oracle's), noise added in float32 as the kernel adds it."""
+# ------------------------------------------------------------------------------------------ scores and choice rules
+def _lead(x: np.ndarray, win: int) -> float:
+    return float(x[win] - np.partition(x, -2)[-2]) if x.size > 1 else np.inf
+
+
+def policy(sd: dict, dobs: dict, num_executors: int, stage_of=None, noise=None) -> SimpleNamespace:
+    """The oracle policy on one observation: stage scores `ss` over the schedulable stages, their winner (arg-max,
+    first maximal index) and its lead over the runner-up; then, for the DAG of stage `stage_of` (default: the winner),
+    the same for the exec scores `es`. Scores are float32 (the oracle's). `noise(items, exec_draw)`, if given, is
+    added to them in float32 as the kernel adds it, before winners and leads are taken (a rule's `noise`)."""
     enc = G.encode(sd, dobs)
     ss = G.stage_scores(sd, dobs, enc)
-    sched = np.flatnonzero(np.asarray(dobs["stage_mask"], dtype=bool))
-    gs = ss.numpy().astype(np.float32) + gumbel_np(seed, env, ctr, sched, exec_draw=stage_key_exec)
-    s_win = int(np.argmax(gs))
-    s_lead = float(gs[s_win] - np.partition(gs, -2)[-2]) if gs.size > 1 else np.inf
-    si = s_win if stage_of is None else stage_of
-    job = G.job_of_stage(dobs, si)
+    s = ss.numpy().astype(np.float32)
+    if noise is not None:
+        s = s + noise(np.flatnonzero(np.asarray(dobs["stage_mask"], dtype=bool)), False)
+    s_win = int(np.argmax(s))
+    job = G.job_of_stage(dobs, s_win if stage_of is None else stage_of)
     es = G.exec_scores(sd, dobs, enc, job, num_executors)
-    ge = es.numpy().astype(np.float32) + gumbel_np(seed, env, ctr, np.arange(es.numel()), exec_draw=True)
-    e_win = int(np.argmax(ge)) if ge.size else 0
-    e_lead = float(ge[e_win] - np.partition(ge, -2)[-2]) if ge.size > 1 else np.inf
-    return SimpleNamespace(ss=ss, es=es, job=job, s_win=s_win, s_lead=s_lead, e_win=e_win, e_lead=e_lead,
-                           s_margin=2.0 * (SCORE_ATOL + SCORE_RTOL * float(ss.abs().max())),
-                           e_margin=2.0 * (SCORE_ATOL + SCORE_RTOL * float(es.abs().max())) if es.numel() else 0.0)
+    e = es.numpy().astype(np.float32)
+    if noise is not None:
+        e = e + noise(np.arange(es.numel()), True)
+    e_win = int(np.argmax(e)) if e.size else 0
+    p = SimpleNamespace(ss=ss, es=es, job=job, s_win=s_win, s_lead=_lead(s, s_win), e_win=e_win, e_lead=_lead(e, e_win),
+                        s_margin=2.0 * (SCORE_ATOL + SCORE_RTOL * float(ss.abs().max())),
+                        e_margin=2.0 * (SCORE_ATOL + SCORE_RTOL * float(es.abs().max())) if es.numel() else 0.0)
+    p.decisive = bool(p.s_lead > p.s_margin and p.e_lead > p.e_margin)
+    return p
 
 
 def _lgprob(p, si: int, ei: int) -> float:
     return float(torch.log_softmax(p.ss, 0)[si] + torch.log_softmax(p.es, 0)[ei])
 
 
-def _walk_env(env_cfg, dataset, env, env_seed, limit, sd, seed, counter, arena, every, plan_cap, helper, complete,
-              max_decisions, stage_key_exec=False):
+class Sampled:
+    """The sampled rollout's rule for the launch parameters (seed, counter): Gumbel-max draws of the device stream,
+    policy checks on every `every`-th sample. stage_key_exec: the stage draw keyed with the exec draw's constant (a
+    wrong stream: the mutation test)."""
+
+    def __init__(self, seed: int, counter: int, every: int = 1, stage_key_exec: bool = False):
+        self.seed, self.counter, self.every, self.stage_key_exec = seed, counter, every, stage_key_exec
+
+    def noise(self, env: int, k: int):
+        return lambda items, exec_draw: gumbel_np(self.seed, env, (self.counter + k) & M64, items,
+                                                  exec_draw=exec_draw or self.stage_key_exec)
+
+    def checks(self, k: int) -> bool:
+        return k % self.every == 0
+
+    @staticmethod
+    def check_choice(where: str, p, si: int, ei: int) -> None:
+        if p.s_lead > p.s_margin and p.s_win != si:
+            raise parity.Mismatch(f"{where}: stage draw: recorded {si}, the reference's Gumbel-max winner is "
+                                  f"{p.s_win} by {p.s_lead:.3e} (margin {p.s_margin:.3e})")
+        if p.e_lead > p.e_margin and p.e_win != ei:
+            raise parity.Mismatch(f"{where}: exec draw: recorded {ei}, the reference's Gumbel-max winner is "
+                                  f"{p.e_win} by {p.e_lead:.3e} (margin {p.e_margin:.3e})")
+
+    @staticmethod
+    def columns(p) -> dict:
+        """`p`: the sample's scores, None where the policy checks skipped the sample."""
+        return dict(audited=p is not None, skipped=p is not None and not p.decisive)
+
+    @staticmethod
+    def summarise(rep: dict, rows: int, what: str) -> None:
+        aud = int(rep["audited"].sum()) if rows else 0
+        skp = int((rep["audited"] & rep["skipped"]).sum()) if rows else 0
+        rep["audited_draws"], rep["skipped_draws"] = aud, skp
+        rep["skip_share"] = skp / aud if aud else 0.0
+        if rep["skip_share"] > MAX_SKIP_SHARE:
+            raise parity.Mismatch(f"{what}: {skp} of {aud} audited draws inside the score margin "
+                                  f"({rep['skip_share']:.1%} > {MAX_SKIP_SHARE:.0%})")
+
+
+class Greedy:
+    """The greedy rollout's rule: no noise, every sample checked, the recorded choice within the margin of the best."""
+
+    @staticmethod
+    def noise(env: int, k: int):
+        return None
+
+    @staticmethod
+    def checks(k: int) -> bool:
+        return True
+
+    @staticmethod
+    def check_choice(where: str, p, si: int, ei: int) -> None:
+        s_best, s_got = float(p.ss.max()), float(p.ss[si])
+        if not s_got >= s_best - p.s_margin:
+            raise parity.Mismatch(f"{where}: stage choice: recorded {si} scores {s_got!r}, the oracle's best ("
+                                  f"{p.s_win}) {s_best!r}: regret {s_best - s_got:.3e} > margin {p.s_margin:.3e}")
+        e_best, e_got = float(p.es.max()), float(p.es[ei])
+        if not e_got >= e_best - p.e_margin:
+            raise parity.Mismatch(f"{where}: exec choice: recorded {ei} scores {e_got!r}, the oracle's best ("
+                                  f"{p.e_win}) {e_best!r}: regret {e_best - e_got:.3e} > margin {p.e_margin:.3e}")
+
+    @staticmethod
+    def columns(p) -> dict:
+        return dict(decisive=p.decisive, s_win=p.s_win, e_win=p.e_win)
+
+    @staticmethod
+    def summarise(rep: dict, rows: int, what: str) -> None:
+        if rows:
+            d = rep["decisive"]
+            rep["decisions"] = rows
+            rep["decisive_share"] = float(d.mean())
+            rep["decisive_exec_nonzero"] = int((d & (rep["e_win"] > 0)).sum())      # exec winner k > 0
+            rep["decisive_stage_nonfirst"] = int((d & (rep["s_win"] > 0)).sum())    # not the first schedulable stage
+
+
+# ------------------------------------------------------------------------------------------ the walk
+def _walk_env(env_cfg, dataset, env, env_seed, limit, sd, rule, arena, plan_cap, helper, complete, max_decisions):
     """One env: the oracle from reset(env_seed, limit) through the recorded samples (arena given: every check of
-    `audit`), or through the reference's own winners (arena None). Returns the per-sample rows of the report."""
+    `audit`), or through the reference's own winners under `rule` (arena None), at most max_decisions of them.
+    Returns the per-sample rows of the report and whether the oracle's episode is over."""
     N = env_cfg["num_executors"]
     limit = float("inf") if limit is None else float(limit)
     o = SparkSchedOracle(env_cfg, dataset)
@@ -189,7 +289,7 @@ def _walk_env(env_cfg, dataset, env, env_seed, limit, sd, seed, counter, arena, 
                 break
             raise parity.Mismatch(f"{where}: recorded after the reference episode ended ({k} decisions)")
         dobs = decima_observation(obs, N)
-        audited = k % every == 0
+        nsch = int(np.count_nonzero(dobs["stage_mask"]))
         if arena is not None:
             r = sample_record(arena, env, k)
             got = sample_observation(arena, env, k, N)
@@ -205,7 +305,6 @@ def _walk_env(env_cfg, dataset, env, env_seed, limit, sd, seed, counter, arena, 
             levels = int(np.asarray(dobs["edge_masks"]).shape[0])
             if max(r["depth"] - 1, 0) != levels:
                 raise parity.Mismatch(f"{where}: depth {r['depth']} vs {levels} oracle edge-mask levels")
-            nsch = int(np.count_nonzero(dobs["stage_mask"]))
             if not 0 <= r["stage_idx"] < nsch:
                 raise parity.Mismatch(f"{where}: stage_idx {r['stage_idx']} outside the {nsch} schedulable stages")
             job = G.job_of_stage(dobs, r["stage_idx"])
@@ -216,33 +315,23 @@ def _walk_env(env_cfg, dataset, env, env_seed, limit, sd, seed, counter, arena, 
                 raise parity.Mismatch(f"{where}: num_exec {r['num_exec']} != exec_idx {r['exec_idx']} + 1")
             if not 0 <= r["exec_idx"] < cap:
                 raise parity.Mismatch(f"{where}: exec_idx {r['exec_idx']} outside commit cap {cap} of job {job}")
-            si, ei = r["stage_idx"], r["exec_idx"]
-        skipped = False
-        if audited or arena is None:
-            p = _policy(sd, dobs, N, seed, env, (counter + k) & M64, stage_of=si if arena is not None else None,
-                        stage_key_exec=stage_key_exec)
-            s_clear, e_clear = p.s_lead > p.s_margin, p.e_lead > p.e_margin
-            skipped = not (s_clear and e_clear)
-            if arena is None:
-                si, ei, job = p.s_win, p.e_win, p.job
-                cap = int(dobs["commit_caps"][job])
-                lg = _lgprob(p, si, ei)
-            else:
-                if s_clear and p.s_win != si:
-                    raise parity.Mismatch(f"{where}: stage draw: recorded {si}, the reference's Gumbel-max winner is "
-                                          f"{p.s_win} by {p.s_lead:.3e} (margin {p.s_margin:.3e})")
-                if e_clear and p.e_win != ei:
-                    raise parity.Mismatch(f"{where}: exec draw: recorded {ei}, the reference's Gumbel-max winner is "
-                                          f"{p.e_win} by {p.e_lead:.3e} (margin {p.e_margin:.3e})")
-                want = _lgprob(p, si, ei)
-                if not abs(r["lgprob"] - want) <= LGPROB_ATOL + LGPROB_RTOL * abs(want):
-                    raise parity.Mismatch(f"{where}: lgprob {r['lgprob']!r} vs oracle {want!r} "
-                                          f"(diff {abs(r['lgprob'] - want):.3e})")
+            si, ei, lg = r["stage_idx"], r["exec_idx"], r["lgprob"]
+        p = None
+        if arena is None:
+            p = policy(sd, dobs, N, noise=rule.noise(env, k))
+            si, ei, job = p.s_win, p.e_win, p.job
+            cap = int(dobs["commit_caps"][job])
+            lg = _lgprob(p, si, ei)
+        elif rule.checks(k):
+            p = policy(sd, dobs, N, stage_of=si, noise=rule.noise(env, k))
+            rule.check_choice(where, p, si, ei)
+            want = _lgprob(p, si, ei)
+            if not abs(lg - want) <= LGPROB_ATOL + LGPROB_RTOL * abs(want):
+                raise parity.Mismatch(f"{where}: lgprob {lg!r} vs oracle {want!r} (diff {abs(lg - want):.3e})")
         plan, exec_path = classify(dobs, job, N, plan_cap, helper)
         rows.append(dict(env=env, k=k, nodes=int(dobs["stage_mask"].shape[0]), dags=len(dobs["dag_ptr"]) - 1,
-                         sched=int(np.count_nonzero(dobs["stage_mask"])), cap=cap, plan=plan, exec_path=exec_path,
-                         audited=bool(audited or arena is None), skipped=bool(skipped), stage_idx=si, exec_idx=ei,
-                         job_idx=job, lgprob=(lg if arena is None else r["lgprob"])))
+                         sched=nsch, cap=cap, plan=plan, exec_path=exec_path, stage_idx=si, exec_idx=ei, job_idx=job,
+                         lgprob=lg, **rule.columns(p)))
         try:
             obs, rew, term, _, info = o.step({"stage_idx": int(si), "num_exec": int(ei) + 1})
         except (ValueError, KeyError) as err:
@@ -253,61 +342,60 @@ def _walk_env(env_cfg, dataset, env, env_seed, limit, sd, seed, counter, arena, 
     if arena is not None and complete and not over:
         raise parity.Mismatch(f"env{env}: {ns} samples recorded, the reference episode goes on (wall {o.wall_time!r}, "
                               f"limit {limit!r})")
-    return rows
+    return rows, over
 
 
-def _report(rows: list[dict], what: str) -> dict:
+def _walk(envs, env_cfg, dataset, seeds, limits, sd, rule, arena, plan_cap, helper, complete, max_decisions, what):
+    rows, over = [], []
+    for e in envs:
+        done = complete if isinstance(complete, bool) else bool(complete[e])
+        r, ov = _walk_env(env_cfg, dataset, e, seeds[e], None if limits is None else limits[e], sd, rule, arena,
+                          plan_cap, helper, done, max_decisions)
+        rows += r
+        over.append(ov)
     rep = {key: np.array([r[key] for r in rows]) for key in rows[0]} if rows else {}
-    aud = int(rep["audited"].sum()) if rows else 0
-    skp = int((rep["audited"] & rep["skipped"]).sum()) if rows else 0
-    rep["audited_draws"], rep["skipped_draws"] = aud, skp
-    rep["skip_share"] = skp / aud if aud else 0.0
+    rep["episode_over"] = over
     rep["plan_counts"] = {p: int((rep["plan"] == p).sum()) if rows else 0 for p in ("lds", "global")}
     rep["exec_path_counts"] = {p: int((rep["exec_path"] == p).sum()) if rows else 0 for p in ("spec", "many", "single")}
-    if rep["skip_share"] > MAX_SKIP_SHARE:
-        raise parity.Mismatch(f"{what}: {skp} of {aud} audited draws inside the score margin "
-                              f"({rep['skip_share']:.1%} > {MAX_SKIP_SHARE:.0%})")
+    rule.summarise(rep, len(rows), what)
     return rep
 
 
-def audit(arena, env_cfg: dict, dataset, seeds, limits, sd: dict, seed: int, counter: int, every: int = 1,
-          plan_cap: int = 0, helper: bool = False, complete: bool = True, envs=None) -> dict:
+def audit(arena, env_cfg: dict, dataset, seeds, limits, sd: dict, rule, plan_cap: int = 0, helper: bool = False,
+          complete=True, envs=None) -> dict:
     """Audits a filled sample arena (host copies: host_arena) of ONE collection (no auto-reset) that started with
-    reset(seeds[e], limits[e]) and ran with the launch parameters (seed, counter); `sd`: the policy's state_dict,
-    fp32 on the CPU. Per env, raising parity.Mismatch on the first failure:
+    reset(seeds[e], limits[e]) and ran under `rule` (Sampled with the launch's seed and counter, or Greedy); `sd`: the
+    policy's state_dict, fp32 on the CPU. Per env, raising parity.Mismatch on the first failure:
 
     Env and features, every sample: a SparkSchedOracle is driven through the recorded (stage_idx, num_exec); before each
     step its Decima observation equals sample_observation under parity.compare_decima (float32 features bit for bit,
     links, dag_ptr and the three masks equal), wall_before equals the oracle's wall time bit for bit, the reward passes
-    parity.reward_close; after the last sample the oracle's episode is over (`complete`).
+    parity.reward_close; after the last sample the oracle's episode is over (`complete`: a bool, or one per env; an
+    env stopped by the launch's max_steps has not ended its episode).
     Record consistency, every sample: num_exec == exec_idx + 1, 0 <= exec_idx < the job's commit cap, job_idx the DAG of
     the stage, the row offsets the running sums of the earlier samples' counts, depth the oracle's edge-mask levels.
-    Policy value, every `every`-th sample: lgprob within 1e-4 + 1e-4 |want| of log_softmax(stage scores)[stage_idx] +
-    log_softmax(exec scores)[exec_idx] of oracle/decima_gnn.py.
-    Draw, the same samples: the Gumbel-max winners of the oracle's scores plus gumbel_np equal the recorded choices
-    wherever the winner leads the runner-up by more than 2 * (1e-5 + 1e-4 max|score|); decisions inside that margin
-    are skipped and counted, more than 2% skipped fails.
+    Policy value, every sample the rule checks: lgprob within 1e-4 + 1e-4 |want| of log_softmax(stage scores)[stage_idx]
+    + log_softmax(exec scores)[exec_idx] of oracle/decima_gnn.py.
+    Choice, the same samples. Sampled: the Gumbel-max winners of the oracle's scores plus gumbel_np equal the recorded
+    choices wherever the winner leads the runner-up by more than 2 * (1e-5 + 1e-4 max|score|); decisions inside that
+    margin are skipped and counted, more than 2% skipped fails. Greedy: the recorded stage's and exec action's scores
+    are within that margin of the best.
 
     Returns the per-sample arrays env, k, nodes, dags, sched, cap (commit cap of the chosen job), plan, exec_path
-    (classify), audited, skipped, and audited_draws, skipped_draws, skip_share, plan_counts, exec_path_counts."""
-    B = arena.cursor.shape[0]
-    rows = []
-    for e in (range(B) if envs is None else envs):
-        rows += _walk_env(env_cfg, dataset, e, seeds[e], None if limits is None else limits[e], sd, seed, counter,
-                          arena, every, plan_cap, helper, complete, 0)
-    return _report(rows, "audit")
+    (classify), stage_idx, exec_idx, job_idx, lgprob, and episode_over (per env), plan_counts, exec_path_counts; under
+    Sampled also audited, skipped and audited_draws, skipped_draws, skip_share; under Greedy decisive, s_win, e_win and
+    decisions, decisive_share, decisive_exec_nonzero, decisive_stage_nonfirst."""
+    return _walk(range(arena.cursor.shape[0]) if envs is None else envs, env_cfg, dataset, seeds, limits, sd, rule,
+                 arena, plan_cap, helper, complete, 0, "audit")
 
 
-def reference_rollout(env_cfg: dict, dataset, seeds, limits, sd: dict, seed: int, counter: int, plan_cap: int = 0,
-                      helper: bool = False, max_decisions: int = 10**9, stage_key_exec: bool = False) -> dict:
+def reference_rollout(env_cfg: dict, dataset, seeds, limits, sd: dict, rule, plan_cap: int = 0, helper: bool = False,
+                      max_decisions: int = 10**9) -> dict:
     """The collection a correct kernel records, without an engine: per env the oracle from reset(seeds[e], limits[e])
-    with the reference's own Gumbel-max winners as actions, until the episode ends. The report of `audit` (every
-    decision counts as audited), plus stage_idx / exec_idx / job_idx / lgprob per sample."""
-    rows = []
-    for e in range(len(seeds)):
-        rows += _walk_env(env_cfg, dataset, e, seeds[e], None if limits is None else limits[e], sd, seed, counter,
-                          None, 1, plan_cap, helper, True, max_decisions, stage_key_exec)
-    return _report(rows, "reference rollout")
+    with the reference's own winners under `rule` as actions, until the episode ends or max_decisions. The report of
+    `audit` (every decision counts as audited)."""
+    return _walk(range(len(seeds)), env_cfg, dataset, seeds, limits, sd, rule, None, plan_cap, helper, True,
+                 max_decisions, "reference rollout")
 
 
 # ------------------------------------------------------------------------------------------ a host-filled arena
@@ -333,13 +421,30 @@ def fill_arena_like_kernel(arena, e, v, f):
     cur[:4] = torch.tensor([cs + 1, cn + n, ce + ne, cg + nj], dtype=torch.int32)
 
 
-def collect_reference(eng, arena, seeds, limits, sd: dict, seed: int, counter: int, stage_key_exec: bool = False):
+def record_like_kernel(arena, e, v, f) -> list[int]:
+    """Env e's current observation into the CPU arena the way the kernel and its host do it: where a region cannot
+    hold it, the kernel's full flag and needs (DecimaPolicy can_act) and the host's growth; then the rows and the
+    record (fill_arena_like_kernel). Returns what the observation needed per region (samples, nodes, edges, DAGs)."""
+    c = v["counts"][e]
+    obs = [1, int(c[_abi.OC_NUM_NODES]), int(c[_abi.OC_NUM_EDGES]), int(c[_abi.OC_NUM_JOBS])]
+    need = [int(arena.cursor[e, i]) + obs[i] for i in range(4)]
+    if any(n > cap for n, cap in zip(need, arena.caps)):
+        arena.cursor[e, _abi.CUR_FULL] = 1
+        arena.cursor[e, _abi.CUR_NEED_NODES] = obs[1]
+        arena.cursor[e, _abi.CUR_NEED_EDGES] = obs[2]
+        arena.cursor[e, _abi.CUR_NEED_DAGS] = obs[3]
+        arena.grow(arena.cursor.numpy())
+    fill_arena_like_kernel(arena, e, v, f)
+    return need
+
+
+def collect_reference(eng, arena, seeds, limits, sd: dict, rule):
     """One collection on the host build of the engine (hostsim.driver.HostEngine `eng`) into the CPU DecimaSampleArena
     `arena`, the way the kernel runs it: per env reset(seeds[e], limits[e]), then until the episode ends (terminated,
-    or wall time >= the limit) the observation rows (fill_arena_like_kernel, the arena grown when a region is full),
-    the action the oracle policy (oracle/decima_gnn.py on the engine's observation and features) draws with gumbel_np
-    on (seed, env, counter + decision index), its oracle log-probability, the wall time, and after the step the
-    reward. stage_key_exec: the stage draw keyed with the exec draw's constant (a wrong stream: the mutation test)."""
+    or wall time >= the limit) the observation rows (record_like_kernel, the arena grown when a region is full), the
+    oracle policy's winner under `rule` (oracle/decima_gnn.py on the engine's observation and features; Sampled: drawn
+    with gumbel_np on (seed, env, counter + decision index), Greedy: the arg-max), its oracle log-probability, the wall
+    time, and after the step the reward."""
     from spark_sched_sim.engine import decima_obs_dict
 
     B, N = eng.num_envs, eng.layout.num_executors
@@ -354,22 +459,10 @@ def collect_reference(eng, arena, seeds, limits, sd: dict, seed: int, counter: i
         for e in range(B):
             if not live[e]:
                 continue
-            c = v["counts"][e]
-            need = [int(arena.cursor[e, 0]) + 1, int(arena.cursor[e, 1]) + int(c[_abi.OC_NUM_NODES]),
-                    int(arena.cursor[e, 2]) + int(c[_abi.OC_NUM_EDGES]),
-                    int(arena.cursor[e, 3]) + int(c[_abi.OC_NUM_JOBS])]
-            if any(n > cap for n, cap in zip(need, arena.caps)):  # the kernel's full flag and needs
-                arena.cursor[e, _abi.CUR_FULL] = 1
-                arena.cursor[e, _abi.CUR_NEED_NODES] = int(c[_abi.OC_NUM_NODES])
-                arena.cursor[e, _abi.CUR_NEED_EDGES] = int(c[_abi.OC_NUM_EDGES])
-                arena.cursor[e, _abi.CUR_NEED_DAGS] = int(c[_abi.OC_NUM_JOBS])
-                arena.grow(arena.cursor.numpy())
-            cs = int(arena.cursor[e, 0])
-            fill_arena_like_kernel(arena, e, v, f)
-            dobs = decima_obs_dict(v, f, e, N)
-            p = _policy(sd, dobs, N, seed, e, (counter + k) & M64, stage_key_exec=stage_key_exec)
+            record_like_kernel(arena, e, v, f)
+            p = policy(sd, decima_obs_dict(v, f, e, N), N, noise=rule.noise(e, k))
             si[e], ne[e] = p.s_win, p.e_win + 1
-            words = arena.rec[e, cs]
+            words = arena.rec[e, int(arena.cursor[e, 0]) - 1]
             words[I32["stage_idx"]], words[I32["job_idx"]] = p.s_win, p.job
             words[I32["exec_idx"]], words[I32["num_exec"]] = p.e_win, p.e_win + 1
             words.view(torch.float32)[_abi.SAMPLE_LGPROB] = _lgprob(p, p.s_win, p.e_win)
@@ -386,3 +479,74 @@ def collect_reference(eng, arena, seeds, limits, sd: dict, seed: int, counter: i
             live[e] = not (bool(c[_abi.OC_TERMINATED]) or float(v["wall_time"][e]) >= limits[e])
         k += 1
     return arena
+
+
+# ------------------------------------------------------------------------------------------ helpers of the tests
+def policy_state(num_executors: int, device="cpu", *, seed: int, noise: float):
+    """A test policy: DecimaScheduler's random init at torch.manual_seed(seed) plus noise * randn on every parameter
+    (as cases.case_decima_policy, so biases matter), drawn on the CPU so the CPU and GPU tests hold the same weights.
+    Returns (module on `device`, its state_dict in fp32 on the CPU)."""
+    from spark_sched_sim.schedulers.decima import DecimaScheduler
+
+    torch.manual_seed(seed)
+    pol = DecimaScheduler(num_executors)
+    for p in pol.parameters():
+        p.data.add_(noise * torch.randn_like(p))
+    sd = {k: v.detach().cpu().float().clone() for k, v in pol.state_dict().items()}
+    return pol.to(device), sd
+
+
+def replanned(rep: dict, plan_cap: int) -> dict:
+    """A reference collection's report for a unit without helper waves and with another plan cap that takes the same
+    trajectories (dr_hbm50 from dr_lds50)."""
+    rep = dict(rep)
+    rep["plan"] = np.where((rep["nodes"] <= plan_cap) & (rep["dags"] <= LDS_PLAN_DAGS), "lds", "global")
+    rep["plan_counts"] = {p: int((rep["plan"] == p).sum()) for p in ("lds", "global")}
+    rep["exec_path_counts"] = {p: 0 for p in ("spec", "many", "single")}
+    return rep
+
+
+def gpu_collect(eng, params, arena, seed: int, counter: int, max_steps=None, budget: int = 0, flags: int = 0):
+    """One collection of the device engine `eng` into `arena`: a launch to the end of every episode, relaunched after
+    each arena growth; with `budget`, launches of that many decisions under SSIM_ROLLOUT_PREEMPT until nothing is added
+    or pending; with `max_steps`, ONE launch of at most that many decisions per env, the arena left as it is. No env
+    may end with error bits. Returns launches, grown (arena growths) and full (the last launch filled the arena)."""
+    launches = grown = 0
+    prev = -1
+    while True:
+        if budget:
+            eng.decima_rollout(params, seed, counter, 64, budget, flags=flags | _abi.SSIM_ROLLOUT_PREEMPT,
+                               samples=arena)
+        else:
+            eng.decima_rollout(params, seed, counter, 10**6 if max_steps is None else max_steps, flags=flags,
+                               samples=arena)
+        launches += 1
+        cur = arena.cursor.cpu().numpy()
+        full = bool((cur[:, _abi.CUR_FULL] != 0).any())
+        if max_steps is not None:
+            break
+        if full:
+            arena.grow(cur)
+            grown += 1
+            continue
+        n = int(cur[:, _abi.CUR_SAMPLES].sum())
+        pend = int(np.count_nonzero(eng.views["counts"][:, _abi.OC_ERR].cpu().numpy() & _abi.SSIM_ERR_PENDING))
+        if not budget or (n == prev and pend == 0):
+            break
+        prev = n
+    torch.cuda.synchronize()
+    err = eng.views["counts"][:, _abi.OC_ERR].cpu().numpy()
+    assert not err.any(), [hex(int(x)) for x in err]
+    return SimpleNamespace(launches=launches, grown=grown, full=full)
+
+
+def arenas_equal(a, b) -> None:
+    """Two host arenas (host_arena) hold the same collection: the cursors, and per env the used prefixes of the
+    records, node rows (as bit patterns), edge rows and DAG rows."""
+    assert np.array_equal(a.cursor, b.cursor)
+    for i in range(a.cursor.shape[0]):
+        ns, nn, ne, nd = (int(x) for x in a.cursor[i, :4])
+        assert np.array_equal(a.rec[i, :ns], b.rec[i, :ns]), f"env {i} records"
+        assert np.array_equal(a.nodes[i, :nn].view(np.uint32), b.nodes[i, :nn].view(np.uint32)), f"env {i} nodes"
+        assert np.array_equal(a.edges[i, :ne], b.edges[i, :ne]), f"env {i} edges"
+        assert np.array_equal(a.dags[i, :nd], b.dags[i, :nd]), f"env {i} dags"

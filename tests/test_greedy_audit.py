@@ -1,6 +1,7 @@
 """The GREEDY persistent Decima rollout (ssim_decima_rollout with SSIM_ROLLOUT_GREEDY; csrc/k_drg_*.hip) audited
-against the CPU oracle by regret (tests/greedy_audit.py), per kernel unit (drg_lds50, drg_hbm50, drg_lds, drg_hbm) on
-test_decima_audit.CASES' envs, seeds, limits, config flags and plans, at most 400 decisions per env.
+against the CPU oracle by regret (tests/decima_audit.py, the Greedy rule), per kernel unit (drg_lds50, drg_hbm50,
+drg_lds, drg_hbm) on test_decima_audit.CASES' envs, seeds, limits, config flags and plans, at most 400 decisions per
+env.
 
 The policy of every case: DecimaScheduler's init at torch.manual_seed(6) plus 0.1 * randn on every parameter. With the
 sampled audit's policy (seed 5, noise 0.05) the greedy exec choice is k = 0 on every decision, so the exec arg-max
@@ -9,7 +10,7 @@ score margin. What a case must contain is asserted from the reference alone (tes
 least 75% of decisions decisive (both leads above their margins), at least 100 decisive decisions with an exec winner
 k > 0, at least 100 with a stage winner that is not the first schedulable stage.
 
-CPU-measured per case (greedy_audit.reference_rollout; every episode ends before the 400-decision cap):
+CPU-measured per case (reference_rollout under Greedy; every episode ends before the 400-decision cap):
   case          decisions (per env)          decisive   exec winner k > 0   stage winner > 0   plan lds / global
   dr_lds_n10    871 (169 / 279 / 268 / 155)  94.8%      718                 748                871 / 0
   dr_lds50      690 (175 / 97 / 217 / 201)   89.1%      576                 569                553 / 137
@@ -29,7 +30,6 @@ import pytest
 import torch
 
 import decima_audit as A
-import greedy_audit as GA
 import parity
 from conftest import ENV_CFG_SMALL
 from spark_sched_sim import _abi
@@ -43,17 +43,7 @@ def greedy_unit(case: dict) -> str:
     return "drg_" + case["unit"][len("dr_"):]
 
 
-def policy_state(num_executors: int, device="cpu"):
-    """The policy of every case (module docstring), drawn on the CPU so the CPU and GPU tests hold the same weights.
-    Returns (module on `device`, its state_dict in fp32 on the CPU)."""
-    from spark_sched_sim.schedulers.decima import DecimaScheduler
-
-    torch.manual_seed(POLICY_SEED)
-    pol = DecimaScheduler(num_executors)
-    for p in pol.parameters():
-        p.data.add_(POLICY_NOISE * torch.randn_like(p))
-    sd = {k: v.detach().cpu().float().clone() for k, v in pol.state_dict().items()}
-    return pol.to(device), sd
+policy_state = functools.partial(A.policy_state, seed=POLICY_SEED, noise=POLICY_NOISE)  # (module docstring)
 
 
 # ------------------------------------------------------------------------------------------ the auditor on a host arena
@@ -65,10 +55,10 @@ def faithful(dataset):
     _, sd = policy_state(MUT_CFG["num_executors"])
     eng = HostEngine(MUT_CFG, len(MUT_SEEDS), dataset)
     arena = DecimaSampleArena(len(MUT_SEEDS), "cpu", cap_samples=8, cap_nodes=64, cap_edges=64, cap_dags=8)
-    GA.collect_reference(eng, arena, MUT_SEEDS, MUT_LIMITS, sd)
+    A.collect_reference(eng, arena, MUT_SEEDS, MUT_LIMITS, sd, A.Greedy())
     assert arena.caps[0] > 8 and arena.caps[1] > 64  # the regions grew
     arena = A.host_arena(arena)
-    rep = GA.audit(arena, MUT_CFG, dataset, MUT_SEEDS, MUT_LIMITS, sd, plan_cap=30)
+    rep = A.audit(arena, MUT_CFG, dataset, MUT_SEEDS, MUT_LIMITS, sd, A.Greedy(), plan_cap=30)
     return arena, sd, rep
 
 
@@ -78,7 +68,7 @@ def test_audit_passes_on_a_faithful_arena(faithful, dataset):
     arena, sd, rep = faithful
     n = int(arena.cursor[:, _abi.CUR_SAMPLES].sum())
     assert n > 100 and rep["decisions"] == n
-    ref = GA.reference_rollout(MUT_CFG, dataset, MUT_SEEDS, MUT_LIMITS, sd, plan_cap=30)
+    ref = A.reference_rollout(MUT_CFG, dataset, MUT_SEEDS, MUT_LIMITS, sd, A.Greedy(), plan_cap=30)
     for key in ("env", "k", "stage_idx", "exec_idx", "job_idx", "nodes", "cap", "plan", "decisive"):
         assert np.array_equal(ref[key], rep[key]), key
     assert np.array_equal(ref["lgprob"].astype(np.float32), rep["lgprob"].astype(np.float32))
@@ -88,7 +78,7 @@ def test_audit_passes_on_a_faithful_arena(faithful, dataset):
 def _sample_scores(arena, sd, e, k):
     dobs = A.sample_observation(arena, e, k, MUT_CFG["num_executors"])
     r = A.sample_record(arena, e, k)
-    return r, GA.greedy_policy(sd, dobs, MUT_CFG["num_executors"], stage_of=r["stage_idx"])
+    return r, A.policy(sd, dobs, MUT_CFG["num_executors"], stage_of=r["stage_idx"])
 
 
 def _first(arena, sd, rep, want):
@@ -177,7 +167,7 @@ def test_audit_fails_on_a_single_mutation(faithful, dataset, name):
     mutate, message = MUTATIONS[name]
     mutate(bad, sd, rep)
     with pytest.raises(parity.Mismatch, match=message):
-        GA.audit(bad, MUT_CFG, dataset, MUT_SEEDS, MUT_LIMITS, sd)
+        A.audit(bad, MUT_CFG, dataset, MUT_SEEDS, MUT_LIMITS, sd, A.Greedy())
 
 
 # ------------------------------------------------------------------------------------------ the GPU cases, on the CPU
@@ -187,14 +177,10 @@ def _reference(name: str):
 
     c = CASES[name]
     if name == "dr_hbm50":  # dr_lds50's trajectories, re-planned
-        rep = dict(_reference("dr_lds50"))
-        rep["plan"] = np.where((rep["nodes"] <= c["plan_cap"]) & (rep["dags"] <= A.LDS_PLAN_DAGS), "lds", "global")
-        rep["plan_counts"] = {p: int((rep["plan"] == p).sum()) for p in ("lds", "global")}
-        rep["exec_path_counts"] = {p: 0 for p in ("spec", "many", "single")}
-        return rep
+        return A.replanned(_reference("dr_lds50"), c["plan_cap"])
     _, sd = policy_state(c["env"]["num_executors"])
-    return GA.reference_rollout(c["env"], generate(0), c["seeds"], c["limits"], sd, plan_cap=c["plan_cap"],
-                                helper=c["waves"] > 1, max_decisions=MAX_DECISIONS)
+    return A.reference_rollout(c["env"], generate(0), c["seeds"], c["limits"], sd, A.Greedy(), plan_cap=c["plan_cap"],
+                               helper=c["waves"] > 1, max_decisions=MAX_DECISIONS)
 
 
 def describe(name: str, rep: dict) -> str:
@@ -223,24 +209,11 @@ def test_gpu_case_reference_collection(name):
 
 # ------------------------------------------------------------------------------------------ the GPU cases
 def _greedy_collect(eng, params, arena, seed, counter, max_steps=None):
-    """One greedy collection into `arena`: a launch to the end of every episode, relaunched after each arena growth;
-    or, with max_steps, ONE launch of at most that many decisions per env into an arena that must hold them. Returns
-    the growths."""
-    grown = 0
-    while True:
-        eng.decima_rollout(params, seed, counter, 10**6 if max_steps is None else max_steps,
-                           flags=_abi.SSIM_ROLLOUT_GREEDY, samples=arena)
-        cur = arena.cursor.cpu().numpy()
-        if (cur[:, _abi.CUR_FULL] != 0).any():
-            assert max_steps is None, "a capped collection's arena must not fill"
-            arena.grow(cur)
-            grown += 1
-            continue
-        break
-    torch.cuda.synchronize()
-    err = eng.views["counts"][:, _abi.OC_ERR].cpu().numpy()
-    assert not err.any(), [hex(int(x)) for x in err]
-    return grown
+    """A.gpu_collect under SSIM_ROLLOUT_GREEDY; with max_steps the arena must hold the one launch. Returns the
+    growths."""
+    got = A.gpu_collect(eng, params, arena, seed, counter, max_steps=max_steps, flags=_abi.SSIM_ROLLOUT_GREEDY)
+    assert max_steps is None or not got.full, "a capped collection's arena must not fill"
+    return got.grown
 
 
 def _engine(c, dataset, gpu_device, check_plan=True):
@@ -285,19 +258,10 @@ def test_greedy_rollout_audit_gpu(gpu_device, dataset, name):
     assert grown > 0
     a = A.host_arena(arena)
     assert int(a.cursor[:, _abi.CUR_SAMPLES].max()) <= MAX_DECISIONS  # (as the reference's: the episodes end first)
-    rep = GA.audit(a, c["env"], dataset, c["seeds"], c["limits"], sd, plan_cap=c["plan_cap"], helper=c["waves"] > 1)
+    rep = A.audit(a, c["env"], dataset, c["seeds"], c["limits"], sd, A.Greedy(), plan_cap=c["plan_cap"],
+                  helper=c["waves"] > 1)
     print(describe(f"{name} ({greedy_unit(c)})", rep))
     check_case_content(c, rep)
-
-
-def _arena_equal(a, b):
-    assert np.array_equal(a.cursor, b.cursor)
-    for i in range(a.cursor.shape[0]):
-        ns, nn, ne, nd = (int(x) for x in a.cursor[i, :4])
-        assert np.array_equal(a.rec[i, :ns], b.rec[i, :ns]), f"env {i} records"
-        assert np.array_equal(a.nodes[i, :nn].view(np.uint32), b.nodes[i, :nn].view(np.uint32)), f"env {i} nodes"
-        assert np.array_equal(a.edges[i, :ne], b.edges[i, :ne]), f"env {i} edges"
-        assert np.array_equal(a.dags[i, :nd], b.dags[i, :nd]), f"env {i} dags"
 
 
 @pytest.mark.gpu
@@ -314,7 +278,7 @@ def test_greedy_ignores_seed_and_counter_gpu(gpu_device, dataset, name):
         _greedy_collect(eng, params, arena, seed, counter, max_steps=96)
         arenas.append(A.host_arena(arena))
     assert (arenas[0].cursor[:, _abi.CUR_SAMPLES] == 96).all()
-    _arena_equal(arenas[0], arenas[1])
+    A.arenas_equal(arenas[0], arenas[1])
 
 
 def _tied_policy(num_executors, device):

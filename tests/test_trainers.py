@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 import torch
 
-from decima_audit import fill_arena_like_kernel as _fill_arena_like_kernel
+import decima_audit as A
 from oracle import trainer_utils as TU
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -474,17 +474,8 @@ def test_arena_buffer_matches_per_step_batches(dataset):
         batches.append(build_batch(tv, tf, envs=torch.tensor(live)))
         envs.append(torch.tensor(live))
         for e in live:
-            need = [int(arena.cursor[e, 0]) + 1, int(arena.cursor[e, 1]) + int(v["counts"][e][_abi.OC_NUM_NODES]),
-                    int(arena.cursor[e, 2]) + int(v["counts"][e][_abi.OC_NUM_EDGES]),
-                    int(arena.cursor[e, 3]) + int(v["counts"][e][_abi.OC_NUM_JOBS])]
-            if any(n > c for n, c in zip(need, arena.caps)):  # the kernel's full flag and needs, the host's growth
-                arena.cursor[e, _abi.CUR_FULL] = 1
-                arena.cursor[e, _abi.CUR_NEED_NODES] = int(v["counts"][e][_abi.OC_NUM_NODES])
-                arena.cursor[e, _abi.CUR_NEED_EDGES] = int(v["counts"][e][_abi.OC_NUM_EDGES])
-                arena.cursor[e, _abi.CUR_NEED_DAGS] = int(v["counts"][e][_abi.OC_NUM_JOBS])
-                arena.grow(arena.cursor.numpy())
-                assert all(n <= c for n, c in zip(need, arena.caps)), (need, arena.caps)  # one growth fits it
-            _fill_arena_like_kernel(arena, e, v, f)
+            need = A.record_like_kernel(arena, e, v, f)  # the kernel's full flag and needs, the host's growth
+            assert all(n <= c for n, c in zip(need, arena.caps)), (need, arena.caps)  # one growth fits it
         eng.rollout(_abi.SSIM_POLICY_RANDOM, 5, 1)
     assert arena.caps[0] >= 12 and arena.caps[1] > 64  # grew
     buf = arena.buffer(torch.zeros(B, dtype=torch.float64))
@@ -561,35 +552,12 @@ def test_decima_rollout_preempted_collection_equals_one_launch(gpu_device, datas
         eng.reset_sampled(_abi.SSIM_RESET_SEED, seeds=seeds, time_limits=limits)
         arena = DecimaSampleArena(B, eng.device, cap_samples=512, cap_nodes=1 << 13, cap_edges=1 << 13,
                                   cap_dags=1 << 11)  # small: the regions grow during the collection
-        launches, prev, grown = 0, -1, 0
-        while True:
-            if budget == 0:
-                eng.decima_rollout(params, 9, 77, 10**6, samples=arena)
-            else:
-                eng.decima_rollout(params, 9, 77, 64, budget, flags=_abi.SSIM_ROLLOUT_PREEMPT, samples=arena)
-            launches += 1
-            cur = arena.cursor.cpu().numpy()
-            if (cur[:, _abi.CUR_FULL] != 0).any():
-                arena.grow(cur)
-                grown += 1
-                continue
-            n = int(cur[:, 0].sum())
-            pend = int(np.count_nonzero(eng.views["counts"][:, _abi.OC_ERR].cpu().numpy() & _abi.SSIM_ERR_PENDING))
-            if budget == 0 or (n == prev and pend == 0):
-                break
-            prev = n
-        assert grown > 0 and (budget == 0 or launches > 10)
-        torch.cuda.synchronize()
-        arenas.append(arena)
+        got = A.gpu_collect(eng, params, arena, 9, 77, budget=budget)
+        assert got.grown > 0 and (budget == 0 or got.launches > 10)
+        arenas.append(A.host_arena(arena))
     a, b = arenas
-    assert torch.equal(a.cursor, b.cursor)
-    assert int(a.cursor[:, 0].min().item()) > 20
-    for i in range(B):
-        ns, nn, ne, nd = (int(x) for x in a.cursor[i, :4].tolist())
-        assert torch.equal(a.rec[i, :ns], b.rec[i, :ns]), f"env {i} records"
-        assert torch.equal(a.nodes[i, :nn], b.nodes[i, :nn]), f"env {i} nodes"
-        assert torch.equal(a.edges[i, :ne], b.edges[i, :ne]), f"env {i} edges"
-        assert torch.equal(a.dags[i, :nd], b.dags[i, :nd]), f"env {i} dags"
+    A.arenas_equal(a, b)
+    assert int(a.cursor[:, 0].min()) > 20
 
 
 @pytest.mark.gpu
