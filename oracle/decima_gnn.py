@@ -7,6 +7,12 @@ with the reference's parameter names, and follows scheduler.py line by line with
 of torch_scatter / torch_sparse / pyg (not installed here):
   NodeEncoder.forward 196-240 (+ _forward_no_mp 242-245), DagEncoder 259-262, GlobalEncoder 272-281,
   StagePolicyNetwork 295-326, ExecPolicyNetwork 342-385, utils.sample/evaluate 19-48.
+
+Two variants budget the kernels' numerics on the CPU (tests/policy_strength.py); at the defaults nothing changes:
+  dtype=torch.float64  the same arithmetic in double (parameters, features, adjacency and the arange / N action
+                       column all cast): what a kernel's scores are compared with where fp32 rounding matters.
+  pol_act=dp_tanh_f32  the score MLPs' Tanh replaced by an fp32 restatement of csrc/decima_policy.h dp_tanh. It only
+                       bounds that formula's documented approximation; no kernel is ever compared with it.
 """
 
 from __future__ import annotations
@@ -16,10 +22,11 @@ import torch
 
 
 def _mlp(sd: dict, prefix: str, x: torch.Tensor, act) -> torch.Tensor:
-    """make_mlp (utils.py:51-70): Linear, act, Linear, act, ..., Linear; keys prefix.{0,2,4,...}."""
+    """make_mlp (utils.py:51-70): Linear, act, Linear, act, ..., Linear; keys prefix.{0,2,4,...}. The parameters are
+    cast to x's dtype (no-op for an fp32 state dict at the default)."""
     idx = sorted({int(k[len(prefix) + 1:].split(".")[0]) for k in sd if k.startswith(prefix + ".")})
     for n, i in enumerate(idx):
-        x = x @ sd[f"{prefix}.{i}.weight"].t() + sd[f"{prefix}.{i}.bias"]
+        x = x @ sd[f"{prefix}.{i}.weight"].to(x.dtype).t() + sd[f"{prefix}.{i}.bias"].to(x.dtype)
         if n < len(idx) - 1:
             x = act(x)
     return x
@@ -33,11 +40,22 @@ def _pol_act(x):  # Tanh (config/decima_tpch.yaml:75-77)
     return torch.tanh(x)
 
 
-def encode(sd: dict, obs: dict, collated_mp: bool | None = None) -> dict:
+def dp_tanh_f32(x: torch.Tensor) -> torch.Tensor:
+    """csrc/decima_policy.h dp_tanh restated in fp32: 1 - 2 / (1 + 2^(2 |x| log2 e)) with the sign restored, x itself
+    below 2^-12 (where the quotient cancels). exp2 and the reciprocal are torch's, within an ulp like the hardware's.
+    Computed in float32 whatever x's dtype, returned in x's dtype."""
+    v = x.to(torch.float32)
+    a = v.abs()
+    e = torch.exp2(a * torch.tensor(2.8853900817779268, dtype=torch.float32))
+    t = 1.0 - 2.0 * torch.reciprocal(e + 1.0)
+    return torch.copysign(torch.where(a < 0.000244140625, a, t), v).to(x.dtype)
+
+
+def encode(sd: dict, obs: dict, collated_mp: bool | None = None, dtype=torch.float32) -> dict:
     """EncoderNetwork.forward for one observation. `collated_mp` forces the message-passing path (the
     reference's collated-batch behaviour when another observation of the batch has levels)."""
     g = obs.get("dag_batch")
-    x = torch.from_numpy(np.array(g.nodes if g is not None else obs["nodes"], dtype=np.float32))
+    x = torch.from_numpy(np.array(g.nodes if g is not None else obs["nodes"], dtype=np.float32)).to(dtype)
     links = np.asarray(g.edge_links if g is not None else obs["edge_links"], dtype=np.int64).reshape(-1, 2)
     masks = np.asarray(obs["edge_masks"], dtype=bool)
     n = x.shape[0]
@@ -53,7 +71,7 @@ def encode(sd: dict, obs: dict, collated_mp: bool | None = None) -> dict:
         h[leaf] = _mlp(sd, "encoder.node_encoder.mlp_update", h_init[leaf], _gnn_act)
         for m in reversed(list(masks)):
             e = links[m]
-            adj = torch.zeros((n, n))
+            adj = torch.zeros((n, n), dtype=dtype)
             for u, v in e:  # dense adjacency, row = parent, col = child
                 adj[u, v] += 1.0
             src = np.zeros(n, dtype=bool)
@@ -68,28 +86,32 @@ def encode(sd: dict, obs: dict, collated_mp: bool | None = None) -> dict:
     ptr = np.asarray(obs["dag_ptr"], dtype=np.int64)
     hn = _mlp(sd, "encoder.dag_encoder.mlp", torch.cat([x, h], dim=1), _gnn_act)
     h_dag = torch.stack([hn[ptr[j]: ptr[j + 1]].sum(0) for j in range(len(ptr) - 1)]) if len(ptr) > 1 \
-        else torch.zeros((0, h.shape[1]))
+        else torch.zeros((0, h.shape[1]), dtype=dtype)
     h_glob = _mlp(sd, "encoder.global_encoder.mlp", h_dag, _gnn_act).sum(0, keepdim=True)
     return {"x": x, "node": h, "dag": h_dag, "glob": h_glob, "ptr": ptr}
 
 
-def stage_scores(sd: dict, obs: dict, enc: dict) -> torch.Tensor:
+def stage_scores(sd: dict, obs: dict, enc: dict, dtype=torch.float32, pol_act=None) -> torch.Tensor:
+    """`enc` must come from encode at the same dtype."""
+    assert enc["x"].dtype == dtype
     m = torch.from_numpy(np.asarray(obs["stage_mask"], dtype=bool))
     ptr = enc["ptr"]
     batch = torch.from_numpy(np.repeat(np.arange(len(ptr) - 1), ptr[1:] - ptr[:-1]))
     k = int(m.sum())
     inp = torch.cat([enc["x"][m], enc["node"][m], enc["dag"][batch[m]], enc["glob"].repeat(k, 1)], dim=1)
-    return _mlp(sd, "stage_policy_network.mlp_score", inp, _pol_act).squeeze(-1)
+    return _mlp(sd, "stage_policy_network.mlp_score", inp, pol_act or _pol_act).squeeze(-1)
 
 
-def exec_scores(sd: dict, obs: dict, enc: dict, job_idx: int, num_executors: int) -> torch.Tensor:
+def exec_scores(sd: dict, obs: dict, enc: dict, job_idx: int, num_executors: int, dtype=torch.float32,
+                pol_act=None) -> torch.Tensor:
+    assert enc["x"].dtype == dtype
     em = torch.from_numpy(np.asarray(obs["exec_mask"], dtype=bool))[job_idx]
     x_dag = enc["x"][int(enc["ptr"][job_idx]), :3].unsqueeze(0)
     h_dag = enc["dag"][job_idx].unsqueeze(0)
-    acts = (torch.arange(num_executors) / num_executors)[em].unsqueeze(1)
+    acts = (torch.arange(num_executors, dtype=dtype) / num_executors)[em].unsqueeze(1)
     k = acts.shape[0]
     inp = torch.cat([torch.cat([x_dag, h_dag], dim=1).repeat(k, 1), enc["glob"].repeat(k, 1), acts], dim=1)
-    return _mlp(sd, "exec_policy_network.mlp_score", inp, _pol_act).squeeze(-1)
+    return _mlp(sd, "exec_policy_network.mlp_score", inp, pol_act or _pol_act).squeeze(-1)
 
 
 def job_of_stage(obs: dict, stage_idx: int) -> int:
@@ -99,8 +121,9 @@ def job_of_stage(obs: dict, stage_idx: int) -> int:
     return int(np.searchsorted(ptr, node, side="right") - 1)
 
 
-def evaluate(scores: torch.Tensor, sel: int) -> tuple[float, float]:
-    """utils.py:25-48 for one observation: (log-prob of `sel`, entropy), clamp_probs included."""
+def evaluate(scores: torch.Tensor, sel: int, dtype=torch.float32) -> tuple[float, float]:
+    """utils.py:25-48 for one observation: (log-prob of `sel`, entropy), clamp_probs included (at dtype's eps)."""
+    scores = scores.to(dtype)
     ex = torch.exp(scores - scores.max())
     probs = ex / (ex.sum() + 1e-16)
     eps = torch.finfo(probs.dtype).eps

@@ -373,27 +373,51 @@ POLICY_CONFIGS = [
     (dict(), 4, 610, 7),
     (dict(num_executors=50, job_arrival_cap=200, beta=5e-3), 2, 620, 11),
 ]
+# The "spread" parameter sets of the policy cases (tests/test_policy_strength.py): the flat set's draw times these
+# gains (encoder, policy networks), at which a 1% error in any layer is visible at the cases' bars.
+SPREAD_GAINS = (1.5, 2.0)
+DENSE50_OVER = dict(num_executors=50, job_arrival_cap=200, job_arrival_rate=1.0e-4)
 
 
-def case_decima_policy(make, dataset, env_cfg, cfg_over, B, seed0, every, device="cpu", max_steps=400):
+def flat_params(num_executors, device, seed0):
+    """The policy cases' standing parameter set: DecimaScheduler's init at torch.manual_seed(seed0) plus 0.05 * randn
+    on every parameter (non-zero biases too, so the bias paths are exercised), drawn on `device`. Returns (module on
+    the device, its state dict in fp32 on the CPU)."""
+    import torch
+
+    from spark_sched_sim.schedulers.decima import DecimaScheduler
+
+    torch.manual_seed(seed0)
+    pol = DecimaScheduler(num_executors).to(device)
+    for p in pol.parameters():
+        p.data.add_(0.05 * torch.randn_like(p))
+    return pol, {k: v.detach().cpu().float() for k, v in pol.state_dict().items()}
+
+
+def spread_params(num_executors, device, seed0):
+    """The spread set: the same recipe drawn on the CPU (decima_audit.policy_state), times SPREAD_GAINS."""
+    import decima_audit
+
+    return decima_audit.policy_state(num_executors, device, seed=seed0, noise=0.05, gains=SPREAD_GAINS)
+
+
+def case_decima_policy(make, dataset, env_cfg, cfg_over, B, seed0, every, device="cpu", max_steps=400,
+                       params=flat_params):
     """The batched Decima GNN (spark_sched_sim/schedulers/decima.py) on the engine's device observation and
     features equals the per-observation CPU fp32 restatement (oracle/decima_gnn.py) on the oracle's
     reference-format observation: stage scores, exec scores of the first schedulable stage's job, and the
-    evaluate_actions log-probabilities / entropies (collated-batch semantics), within 1e-5."""
+    evaluate_actions log-probabilities / entropies (collated-batch semantics), within 1e-5. `params`: the parameter
+    factory (flat_params or spread_params)."""
     import torch
 
     from oracle import decima_gnn as G
-    from spark_sched_sim.schedulers.decima import DecimaScheduler, build_batch
+    from spark_sched_sim.schedulers.decima import build_batch
 
     cfg = dict(env_cfg, **cfg_over)
     N = cfg["num_executors"]
     eng = make(cfg, B, dataset, 0)
     oracles = [SparkSchedOracle(cfg, dataset) for _ in range(B)]
-    torch.manual_seed(seed0)
-    pol = DecimaScheduler(N).to(device)
-    for p in pol.parameters():  # non-zero biases too, so the bias paths are exercised
-        p.data.add_(0.05 * torch.randn_like(p))
-    sd = {k: v.detach().cpu().float() for k, v in pol.state_dict().items()}
+    pol, sd = params(N, device, seed0)
     seen = {"checks": 0, "mp": 0}
     tol = dict(rtol=1e-5, atol=1e-5)
 
@@ -510,7 +534,8 @@ def _is_none_action(a: dict, rows) -> bool:
     return got == [[-1] * n, [1] * n, [-1] * n, [0] * n, [0.0] * n]
 
 
-def case_decima_fused(make, dataset, env_cfg, cfg_over, B, seed0, iters=12, device="cuda:0", preroll=150, expect=()):
+def case_decima_fused(make, dataset, env_cfg, cfg_over, B, seed0, iters=12, device="cuda:0", preroll=150, expect=(),
+                      params=flat_params, oracle_dtype=None, oracle_every=4, aux_calls=True):
     """ssim_decima_policy (one fused kernel) vs the PyTorch DecimaScheduler on the same device observations, and vs
     the per-observation CPU restatement (oracle/decima_gnn.py) on the reference-format observation read back from the
     device: stage scores of every schedulable node, exec scores of the sampled DAG, and the log-probability of the
@@ -520,11 +545,15 @@ def case_decima_fused(make, dataset, env_cfg, cfg_over, B, seed0, iters=12, devi
     16 schedulable stages, "cap64": a sampled DAG with more than 64 exec actions), each of which must have been checked.
     On the first decision, one call with an env_mask (cleared envs return the "none" action, the others exactly the
     unmasked call's) and one with node_cap below the largest node count (overflow counts the envs above it, which
-    return the "none" action; the rest exactly the full-cap call's)."""
+    return the "none" action; the rest exactly the full-cap call's; aux_calls=False leaves these two calls out, for a
+    batch too small for them). `params`: the parameter factory (flat_params or spread_params); oracle_dtype: the
+    oracle's precision (default float32; torch.float64 at the spread set); oracle_every: 4, or 1 for every env."""
     import torch
 
     from oracle import decima_gnn as G
-    from spark_sched_sim.schedulers.decima import DecimaScheduler, build_batch
+    from spark_sched_sim.schedulers.decima import build_batch
+
+    odt = oracle_dtype or torch.float32
 
     cfg = dict(env_cfg, **cfg_over)
     N = cfg["num_executors"]
@@ -532,11 +561,7 @@ def case_decima_fused(make, dataset, env_cfg, cfg_over, B, seed0, iters=12, devi
     eng.reset(seeds=[seed0 + i for i in range(B)])
     if preroll:
         eng.rollout(_abi.SSIM_POLICY_RANDOM, seed0, preroll)
-    torch.manual_seed(seed0)
-    pol = DecimaScheduler(N).to(device)
-    for p in pol.parameters():
-        p.data.add_(0.05 * torch.randn_like(p))
-    sd = {k: v.detach().cpu().float() for k, v in pol.state_dict().items()}
+    pol, sd = params(N, device, seed0)
     checked = 0
     seen = {"nodes64": 0, "sched16": 0, "cap64": 0, "oracle": 0}
     for it in range(iters):
@@ -550,7 +575,7 @@ def case_decima_fused(make, dataset, env_cfg, cfg_over, B, seed0, iters=12, devi
         hv = eng.host_views()
         hf = {key: x.cpu().numpy() for key, x in feats.items()}
         nn = np.asarray(hv["counts"])[:, _abi.OC_NUM_NODES].astype(np.int64)
-        if it == 0:
+        if it == 0 and aux_calls:
             keep = torch.tensor([e % 3 != 1 for e in range(B)], device=device)
             fm = pol.schedule_fused(eng, feats, seed=7, counter=it, env_mask=keep)
             assert int(fm["overflow"].item()) == 0
@@ -588,16 +613,16 @@ def case_decima_fused(make, dataset, env_cfg, cfg_over, B, seed0, iters=12, devi
             checked += 1
             paths = [name for name, hit in (("nodes64", int(nn[e]) > 64), ("sched16", rows.numel() > 16),
                                             ("cap64", cap > 64)) if hit]
-            if (e + it) % 4 == 0 or any(seen[name] < 3 for name in paths):
+            if (e + it) % oracle_every == 0 or any(seen[name] < 3 for name in paths):
                 # the oracle on the reference-format observation (oracle/decima_gnn.py), the same tolerances
                 ro = decima_obs_dict(hv, hf, e, N)
-                enc = G.encode(sd, ro)
-                rs = G.stage_scores(sd, ro, enc)
-                assert torch.allclose(got, rs, rtol=1e-4, atol=1e-5), f"env{e} it{it} stage scores vs oracle"
+                enc = G.encode(sd, ro, dtype=odt)
+                rs = G.stage_scores(sd, ro, enc, dtype=odt)
+                assert torch.allclose(got.to(odt), rs, rtol=1e-4, atol=1e-5), f"env{e} it{it} stage scores vs oracle"
                 assert G.job_of_stage(ro, int(si[e])) == int(ji[e]), f"env{e} it{it} job of the stage"
-                re_ = G.exec_scores(sd, ro, enc, int(ji[e]), N)
+                re_ = G.exec_scores(sd, ro, enc, int(ji[e]), N, dtype=odt)
                 assert re_.numel() == cap, f"env{e} it{it} exec cap {cap} vs oracle {re_.numel()}"
-                assert torch.allclose(fo["exec_scores"][e, :cap].cpu(), re_, rtol=1e-4, atol=1e-5), \
+                assert torch.allclose(fo["exec_scores"][e, :cap].cpu().to(odt), re_, rtol=1e-4, atol=1e-5), \
                     f"env{e} it{it} exec scores vs oracle"
                 want_o = float(torch.log_softmax(rs, 0)[int(si[e])] + torch.log_softmax(re_, 0)[int(ei[e])])
                 assert abs(float(lg[e]) - want_o) <= 1e-4 + 1e-4 * abs(want_o), f"env{e} it{it} lgprob vs oracle"

@@ -166,19 +166,20 @@ def _lead(x: np.ndarray, win: int) -> float:
     return float(x[win] - np.partition(x, -2)[-2]) if x.size > 1 else np.inf
 
 
-def policy(sd: dict, dobs: dict, num_executors: int, stage_of=None, noise=None) -> SimpleNamespace:
+def policy(sd: dict, dobs: dict, num_executors: int, stage_of=None, noise=None, dtype=torch.float32) -> SimpleNamespace:
     """The oracle policy on one observation: stage scores `ss` over the schedulable stages, their winner (arg-max,
     first maximal index) and its lead over the runner-up; then, for the DAG of stage `stage_of` (default: the winner),
-    the same for the exec scores `es`. Scores are float32 (the oracle's). `noise(items, exec_draw)`, if given, is
-    added to them in float32 as the kernel adds it, before winners and leads are taken (a rule's `noise`)."""
-    enc = G.encode(sd, dobs)
-    ss = G.stage_scores(sd, dobs, enc)
+    the same for the exec scores `es`. Scores are the oracle's at `dtype` (float32, or float64 for the cases with a
+    derived lgprob bar). `noise(items, exec_draw)`, if given, is added to them in float32 as the kernel adds it, before
+    winners and leads are taken (a rule's `noise`)."""
+    enc = G.encode(sd, dobs, dtype=dtype)
+    ss = G.stage_scores(sd, dobs, enc, dtype=dtype)
     s = ss.numpy().astype(np.float32)
     if noise is not None:
         s = s + noise(np.flatnonzero(np.asarray(dobs["stage_mask"], dtype=bool)), False)
     s_win = int(np.argmax(s))
     job = G.job_of_stage(dobs, s_win if stage_of is None else stage_of)
-    es = G.exec_scores(sd, dobs, enc, job, num_executors)
+    es = G.exec_scores(sd, dobs, enc, job, num_executors, dtype=dtype)
     e = es.numpy().astype(np.float32)
     if noise is not None:
         e = e + noise(np.arange(es.numel()), True)
@@ -271,10 +272,19 @@ class Greedy:
 
 
 # ------------------------------------------------------------------------------------------ the walk
-def _walk_env(env_cfg, dataset, env, env_seed, limit, sd, rule, arena, plan_cap, helper, complete, max_decisions):
+def lgprob_bar_of(want: float, lgprob_bar=None) -> float:
+    """The bar on a recorded lgprob: 1e-4 + 1e-4 |want|, or the case's derived absolute bar where that is smaller."""
+    std = LGPROB_ATOL + LGPROB_RTOL * abs(want)
+    return std if lgprob_bar is None else min(std, lgprob_bar)
+
+
+def _walk_env(env_cfg, dataset, env, env_seed, limit, sd, rule, arena, plan_cap, helper, complete, max_decisions,
+              ref):
     """One env: the oracle from reset(env_seed, limit) through the recorded samples (arena given: every check of
     `audit`), or through the reference's own winners under `rule` (arena None), at most max_decisions of them.
-    Returns the per-sample rows of the report and whether the oracle's episode is over."""
+    `ref`: the oracle's dtype, the derived lgprob bar (or None) and `observe` (or None), called with (env, k, the
+    Decima observation, stage_idx, exec_idx) of every decision. Returns the per-sample rows of the report and whether
+    the oracle's episode is over."""
     N = env_cfg["num_executors"]
     limit = float("inf") if limit is None else float(limit)
     o = SparkSchedOracle(env_cfg, dataset)
@@ -318,16 +328,20 @@ def _walk_env(env_cfg, dataset, env, env_seed, limit, sd, rule, arena, plan_cap,
             si, ei, lg = r["stage_idx"], r["exec_idx"], r["lgprob"]
         p = None
         if arena is None:
-            p = policy(sd, dobs, N, noise=rule.noise(env, k))
+            p = policy(sd, dobs, N, noise=rule.noise(env, k), dtype=ref.dtype)
             si, ei, job = p.s_win, p.e_win, p.job
             cap = int(dobs["commit_caps"][job])
             lg = _lgprob(p, si, ei)
         elif rule.checks(k):
-            p = policy(sd, dobs, N, stage_of=si, noise=rule.noise(env, k))
+            p = policy(sd, dobs, N, stage_of=si, noise=rule.noise(env, k), dtype=ref.dtype)
             rule.check_choice(where, p, si, ei)
             want = _lgprob(p, si, ei)
-            if not abs(lg - want) <= LGPROB_ATOL + LGPROB_RTOL * abs(want):
-                raise parity.Mismatch(f"{where}: lgprob {lg!r} vs oracle {want!r} (diff {abs(lg - want):.3e})")
+            bar = lgprob_bar_of(want, ref.lgprob_bar)
+            if not abs(lg - want) <= bar:
+                raise parity.Mismatch(f"{where}: lgprob {lg!r} vs oracle {want!r} (diff {abs(lg - want):.3e}, bar "
+                                      f"{bar:.3e})")
+        if ref.observe is not None:
+            ref.observe(env, k, dobs, int(si), int(ei))
         plan, exec_path = classify(dobs, job, N, plan_cap, helper)
         rows.append(dict(env=env, k=k, nodes=int(dobs["stage_mask"].shape[0]), dags=len(dobs["dag_ptr"]) - 1,
                          sched=nsch, cap=cap, plan=plan, exec_path=exec_path, stage_idx=si, exec_idx=ei, job_idx=job,
@@ -345,12 +359,14 @@ def _walk_env(env_cfg, dataset, env, env_seed, limit, sd, rule, arena, plan_cap,
     return rows, over
 
 
-def _walk(envs, env_cfg, dataset, seeds, limits, sd, rule, arena, plan_cap, helper, complete, max_decisions, what):
+def _walk(envs, env_cfg, dataset, seeds, limits, sd, rule, arena, plan_cap, helper, complete, max_decisions, what,
+          dtype=torch.float32, lgprob_bar=None, observe=None):
+    ref = SimpleNamespace(dtype=dtype, lgprob_bar=lgprob_bar, observe=observe)
     rows, over = [], []
     for e in envs:
         done = complete if isinstance(complete, bool) else bool(complete[e])
         r, ov = _walk_env(env_cfg, dataset, e, seeds[e], None if limits is None else limits[e], sd, rule, arena,
-                          plan_cap, helper, done, max_decisions)
+                          plan_cap, helper, done, max_decisions, ref)
         rows += r
         over.append(ov)
     rep = {key: np.array([r[key] for r in rows]) for key in rows[0]} if rows else {}
@@ -362,7 +378,7 @@ def _walk(envs, env_cfg, dataset, seeds, limits, sd, rule, arena, plan_cap, help
 
 
 def audit(arena, env_cfg: dict, dataset, seeds, limits, sd: dict, rule, plan_cap: int = 0, helper: bool = False,
-          complete=True, envs=None) -> dict:
+          complete=True, envs=None, **ref) -> dict:
     """Audits a filled sample arena (host copies: host_arena) of ONE collection (no auto-reset) that started with
     reset(seeds[e], limits[e]) and ran under `rule` (Sampled with the launch's seed and counter, or Greedy); `sd`: the
     policy's state_dict, fp32 on the CPU. Per env, raising parity.Mismatch on the first failure:
@@ -375,7 +391,9 @@ def audit(arena, env_cfg: dict, dataset, seeds, limits, sd: dict, rule, plan_cap
     Record consistency, every sample: num_exec == exec_idx + 1, 0 <= exec_idx < the job's commit cap, job_idx the DAG of
     the stage, the row offsets the running sums of the earlier samples' counts, depth the oracle's edge-mask levels.
     Policy value, every sample the rule checks: lgprob within 1e-4 + 1e-4 |want| of log_softmax(stage scores)[stage_idx]
-    + log_softmax(exec scores)[exec_idx] of oracle/decima_gnn.py.
+    + log_softmax(exec scores)[exec_idx] of oracle/decima_gnn.py. `ref`: dtype=torch.float64 takes the oracle in double,
+    lgprob_bar=x an absolute bar x wherever it is below the standing one (the cases with a bar derived from the
+    reference, tests/policy_strength.py), observe=f is called with (env, k, observation, stage_idx, exec_idx).
     Choice, the same samples. Sampled: the Gumbel-max winners of the oracle's scores plus gumbel_np equal the recorded
     choices wherever the winner leads the runner-up by more than 2 * (1e-5 + 1e-4 max|score|); decisions inside that
     margin are skipped and counted, more than 2% skipped fails. Greedy: the recorded stage's and exec action's scores
@@ -386,16 +404,16 @@ def audit(arena, env_cfg: dict, dataset, seeds, limits, sd: dict, rule, plan_cap
     Sampled also audited, skipped and audited_draws, skipped_draws, skip_share; under Greedy decisive, s_win, e_win and
     decisions, decisive_share, decisive_exec_nonzero, decisive_stage_nonfirst."""
     return _walk(range(arena.cursor.shape[0]) if envs is None else envs, env_cfg, dataset, seeds, limits, sd, rule,
-                 arena, plan_cap, helper, complete, 0, "audit")
+                 arena, plan_cap, helper, complete, 0, "audit", **ref)
 
 
 def reference_rollout(env_cfg: dict, dataset, seeds, limits, sd: dict, rule, plan_cap: int = 0, helper: bool = False,
-                      max_decisions: int = 10**9) -> dict:
+                      max_decisions: int = 10**9, **ref) -> dict:
     """The collection a correct kernel records, without an engine: per env the oracle from reset(seeds[e], limits[e])
     with the reference's own winners under `rule` as actions, until the episode ends or max_decisions. The report of
-    `audit` (every decision counts as audited)."""
+    `audit` (every decision counts as audited). `ref`: dtype and observe, as in `audit`."""
     return _walk(range(len(seeds)), env_cfg, dataset, seeds, limits, sd, rule, None, plan_cap, helper, True,
-                 max_decisions, "reference rollout")
+                 max_decisions, "reference rollout", **ref)
 
 
 # ------------------------------------------------------------------------------------------ a host-filled arena
@@ -482,16 +500,22 @@ def collect_reference(eng, arena, seeds, limits, sd: dict, rule):
 
 
 # ------------------------------------------------------------------------------------------ helpers of the tests
-def policy_state(num_executors: int, device="cpu", *, seed: int, noise: float):
+def policy_state(num_executors: int, device="cpu", *, seed: int, noise: float, gains=(1.0, 1.0)):
     """A test policy: DecimaScheduler's random init at torch.manual_seed(seed) plus noise * randn on every parameter
     (as cases.case_decima_policy, so biases matter), drawn on the CPU so the CPU and GPU tests hold the same weights.
-    Returns (module on `device`, its state_dict in fp32 on the CPU)."""
+    `gains` = (g_enc, g_pol) then multiply every encoder.* parameter by g_enc and every parameter of the two policy
+    networks by g_pol: the "spread" sets of tests/policy_strength.py. Returns (module on `device`, its state_dict in
+    fp32 on the CPU)."""
     from spark_sched_sim.schedulers.decima import DecimaScheduler
 
     torch.manual_seed(seed)
     pol = DecimaScheduler(num_executors)
     for p in pol.parameters():
         p.data.add_(noise * torch.randn_like(p))
+    for name, p in pol.named_parameters():
+        g = gains[0] if name.startswith("encoder.") else gains[1]
+        if g != 1.0:
+            p.data.mul_(g)
     sd = {k: v.detach().cpu().float().clone() for k, v in pol.state_dict().items()}
     return pol.to(device), sd
 

@@ -19,6 +19,16 @@ CPU-measured per case (reference_rollout under Greedy; every episode ends before
   dr_hbm_n127   284 (137 / 147)              83.5%      227                 193                211 / 73  (cap > 64: 69)
   dr_hbm_n3     581 (226 / 191 / 164)        93.5%      411                 527                49 / 532
 (the two winner columns count decisive decisions only); dr_lds50's helper paths: spec 238, many 169, single 283.
+
+Spread cases (SPREAD_CASES; see test_decima_audit.py): the same draw times SPREAD_GAINS = (1, 1.5), 2 envs, the oracle
+in float64, the lgprob held to the bar derived from the case's reference collection, the same three content
+conditions. The drg_hbm shape is dr_hbm_n3: within dr_hbm_n127's first 160 decisions only a third are decisive at any
+gains tried. CPU-measured (the fp32 figures move by about a quarter between hosts):
+  case               decisions (per env)  decisive  exec k > 0  stage > 0  |fp32 - fp64|  |dp_tanh - fp64|  bar
+  dr_lds50_spread    256 (111 / 145)      89.8%     116         214        7.93e-7        1.02e-6           1.64e-5
+                     lds 256; spec 106, many 58, single 92
+  dr_hbm_n3_spread   248 (142 / 106)      96.4%     174         232        8.75e-7        7.24e-7           1.40e-5
+                     lds 13, global 235; 210 samples above 64 nodes
 """
 
 import copy
@@ -33,7 +43,8 @@ import decima_audit as A
 import parity
 from conftest import ENV_CFG_SMALL
 from spark_sched_sim import _abi
-from test_decima_audit import CASES, DENSE50, MUT_CFG, MUT_LIMITS, MUT_SEEDS, seen_paths
+from test_decima_audit import (CASES, DENSE50, MUT_CFG, MUT_LIMITS, MUT_SEEDS, decisions_range, seen_paths,
+                               spread_reference)
 
 POLICY_SEED, POLICY_NOISE, MAX_DECISIONS = 6, 0.1, 400
 MIN_DECISIVE_SHARE, MIN_EXEC_NONZERO, MIN_STAGE_NONFIRST = 0.75, 100, 100
@@ -44,6 +55,17 @@ def greedy_unit(case: dict) -> str:
 
 
 policy_state = functools.partial(A.policy_state, seed=POLICY_SEED, noise=POLICY_NOISE)  # (module docstring)
+
+# "Spread" cases (module docstring): a case of test_decima_audit.CASES with 2 envs, limits under which each env records
+# 60..150 decisions, the parameters times SPREAD_GAINS, the oracle in float64 and the lgprob bar derived from the
+# reference's own collection (tests/policy_strength.py).
+SPREAD_GAINS = (1.0, 1.5)
+SPREAD_CASES = {
+    "dr_lds50_spread": dict(CASES["dr_lds50"], seeds=[700, 701], limits=[4.0e4, 3.5e4], gains=SPREAD_GAINS,
+                            must=("plan_lds", "spec", "many", "single")),
+    "dr_hbm_n3_spread": dict(CASES["dr_hbm_n3"], seeds=[700, 701], limits=[4.0e5, 5.0e5], gains=SPREAD_GAINS),
+}
+ALL_CASES = {**CASES, **SPREAD_CASES}
 
 
 # ------------------------------------------------------------------------------------------ the auditor on a host arena
@@ -175,9 +197,12 @@ def test_audit_fails_on_a_single_mutation(faithful, dataset, name):
 def _reference(name: str):
     from spark_sched_sim.data_samplers.synthetic_tpch import generate
 
-    c = CASES[name]
+    c = ALL_CASES[name]
     if name == "dr_hbm50":  # dr_lds50's trajectories, re-planned
         return A.replanned(_reference("dr_lds50"), c["plan_cap"])
+    if "gains" in c:
+        return spread_reference(c, A.Greedy(), policy=lambda N, gains: policy_state(N, gains=gains),
+                                max_decisions=MAX_DECISIONS)
     _, sd = policy_state(c["env"]["num_executors"])
     return A.reference_rollout(c["env"], generate(0), c["seeds"], c["limits"], sd, A.Greedy(), plan_cap=c["plan_cap"],
                                helper=c["waves"] > 1, max_decisions=MAX_DECISIONS)
@@ -198,13 +223,22 @@ def check_case_content(c: dict, rep: dict):
     assert all(seen[m] > 0 for m in c["must"]), seen
 
 
-@pytest.mark.parametrize("name", list(CASES))
+@pytest.mark.parametrize("name", list(ALL_CASES))
 def test_gpu_case_reference_collection(name):
     """What a correct greedy kernel records for a GPU case, from the reference alone: the three content conditions of
-    the module docstring, and every path the case demands (both plans, the three helper paths, caps above 64)."""
+    the module docstring, and every path the case demands (both plans, the three helper paths, caps above 64). A
+    spread case: 60..150 decisions per env, and a derived lgprob bar between its floor and the standing bar's 1e-4."""
+    c = ALL_CASES[name]
     rep = _reference(name)
     print(describe(name, rep))
-    check_case_content(CASES[name], rep)
+    check_case_content(c, rep)
+    if "gains" in c:
+        print(f"{name}: lgprob |fp32 - fp64| {rep['lg_err_fp32']:.3e}, |restated dp_tanh - fp64| "
+              f"{rep['lg_err_act']:.3e}, derived bar {rep['lgprob_bar']:.3e}")
+        assert 2e-6 <= rep["lgprob_bar"] < A.LGPROB_ATOL
+        lo, hi = decisions_range(c)
+        per_env = [int((rep["env"] == e).sum()) for e in range(len(c["seeds"]))]
+        assert all(lo <= n <= hi for n in per_env), per_env
 
 
 # ------------------------------------------------------------------------------------------ the GPU cases
@@ -245,13 +279,15 @@ def _roomy_arena(B, device, samples):  # (never fills within `samples` decisions
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("name", list(CASES))
+@pytest.mark.parametrize("name", list(ALL_CASES))
 def test_greedy_rollout_audit_gpu(gpu_device, dataset, name):
     """One SSIM_ROLLOUT_GREEDY collection of the case's unit into a small sample arena (it grows at least once), then
-    the regret audit of every sample; the unit's name, the plan, the case's content and paths are asserted."""
-    c = CASES[name]
+    the regret audit of every sample; the unit's name, the plan, the case's content and paths are asserted. A spread
+    case: the oracle in float64 and the lgprob bar derived from the reference's collection of the case."""
+    c = ALL_CASES[name]
     B, N = len(c["seeds"]), c["env"]["num_executors"]
-    pol, sd = policy_state(N, gpu_device)
+    pol, sd = policy_state(N, gpu_device, gains=c.get("gains", (1.0, 1.0)))
+    ref = dict(dtype=torch.float64, lgprob_bar=_reference(name)["lgprob_bar"]) if "gains" in c else {}
     eng = _engine(c, dataset, gpu_device)
     arena = _small_arena(B, eng.device)
     grown = _greedy_collect(eng, pol.packed_params(gpu_device), arena, 9, 77)
@@ -259,7 +295,7 @@ def test_greedy_rollout_audit_gpu(gpu_device, dataset, name):
     a = A.host_arena(arena)
     assert int(a.cursor[:, _abi.CUR_SAMPLES].max()) <= MAX_DECISIONS  # (as the reference's: the episodes end first)
     rep = A.audit(a, c["env"], dataset, c["seeds"], c["limits"], sd, A.Greedy(), plan_cap=c["plan_cap"],
-                  helper=c["waves"] > 1)
+                  helper=c["waves"] > 1, **ref)
     print(describe(f"{name} ({greedy_unit(c)})", rep))
     check_case_content(c, rep)
 

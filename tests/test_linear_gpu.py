@@ -180,3 +180,108 @@ def test_hipmlp3_backward_is_deterministic(gpu_device):
         fused(x).backward(g)
         out.append([x.grad.clone()] + [p.grad.clone() for p in fused.parameters()])
     assert all(torch.equal(a, b) for a, b in zip(out[0], out[1]))
+
+
+# ---- the same chains at a trained policy's scale: weights times a gain and inputs over four decades, so that the hidden
+# pre-activations reach every range of the kernels' activation code (csrc/k_linear.hip mlp_tanh: the polynomial below
+# 1/8, the exp quotient above it, saturation to exactly +-1 where the 1 - h^2 derivative is 0), against the same
+# nn.Sequential in float64
+
+# The seed: torch fp32 on the CPU reaches 0.03 .. 0.26 of the bar of the float64 reference over seeds 1000..1011 (the
+# out = 1 shapes' last-layer gradients sum 1000 terms of order 1 to a total of order 1); 1002 leaves it under 0.09.
+_WIDE_ROWS, _WIDE_GAIN, _WIDE_TINY_ROWS, _WIDE_SEED = 1000, 3.0, 32, 1002
+_WIDE_RANGES = {"tiny": (0.0, 2.0 ** -12), "cutover": (0.1, 0.15), "saturated": (9.0, float("inf"))}
+
+
+def _share_of_bar(a, b):
+    """max |a - b| relative to the file's bar 1e-5 * max(1, max |b|); b is the float64 reference."""
+    return float((a.detach().cpu().double() - b).abs().max()) / (1e-5 * max(1.0, float(b.abs().max())))
+
+
+def _run(m, x, g):
+    """(output, input gradient, the six parameter gradients) of the chain m at x under the upstream gradient g."""
+    m.zero_grad()
+    x = x.clone().requires_grad_(True)
+    y = m(x)
+    y.backward(g)
+    return [y.detach(), x.grad] + [p.grad for p in m.parameters()]
+
+
+_wide_cache = {}
+
+
+def _wide_case(shape):
+    """The fused chain (on the CPU), the inputs, the upstream gradient, the float64 reference's results, torch fp32's
+    results on the CPU and the count of hidden pre-activations of the reference per range of _WIDE_RANGES. Rows scale
+    as 10^U(-2, 1); the first _WIDE_TINY_ROWS rows are moved along one first-layer weight row so that this unit's
+    pre-activation is a chosen value below 2^-12 (the density of a pre-activation near 0 would leave about one)."""
+    if shape in _wide_cache:
+        return _wide_cache[shape]
+    d0, hid, out, act = shape
+    gen = torch.Generator().manual_seed(_WIDE_SEED + d0)
+    torch.manual_seed(_WIDE_SEED + d0)  # (the modules' init draws from the global generator)
+    fused, ref32 = _mlp_pair(d0, list(hid), out, act, "cpu")
+    with torch.no_grad():
+        for p in ref32.parameters():
+            p.mul_(_WIDE_GAIN)
+        fused.load_state_dict(ref32.state_dict())
+        x = torch.randn(_WIDE_ROWS, d0, generator=gen) * 10.0 ** (3.0 * torch.rand(_WIDE_ROWS, 1, generator=gen) - 2.0)
+        w, b = ref32[0].weight.double(), ref32[0].bias.double()
+        for r in range(_WIDE_TINY_ROWS):
+            j = r % hid[0]
+            t = (2.0 * float(torch.rand((), generator=gen)) - 1.0) * 2.0 ** -13
+            xr = x[r].double()
+            x[r] = (xr - w[j] * ((w[j] @ xr + b[j] - t) / (w[j] @ w[j]))).float()
+        import copy
+
+        ref64 = copy.deepcopy(ref32).double()
+        pre1 = ref64[0](x.double())
+        pre2 = ref64[2](ref64[1](pre1.clone()))
+        pre = torch.cat([pre1.reshape(-1), pre2.reshape(-1)]).abs()
+        counts = {k: int(((pre >= lo) & (pre <= hi)).sum()) if k != "tiny" else int((pre < hi).sum())
+                  for k, (lo, hi) in _WIDE_RANGES.items()}
+    g = _kinks_masked(ref64, x.double(), torch.randn(_WIDE_ROWS, out, generator=gen).double())  # (fp32 values)
+    case = dict(fused=fused, x=x, g=g.float(), want=_run(ref64, x.double(), g), cpu32=_run(ref32, x, g.float()),
+                counts=counts)
+    _wide_cache[shape] = case
+    return case
+
+
+_WIDE_NAMES = ["forward", "input gradient"] + [f"parameter {k} gradient" for k in range(6)]
+
+
+@pytest.mark.parametrize("shape", [(s[0], tuple(s[1]), s[2], s[3]) for s in _MLP_SHAPES],
+                         ids=lambda s: f"{s[0]}-{s[1][0]}-{s[2]}-{s[3]}")
+def test_wide_range_reference_is_sound(shape):
+    """The wide-range case from the reference alone: for the Tanh shapes at least 10 hidden pre-activations in each of
+    |v| < 2^-12, 0.1 <= |v| <= 0.15 and |v| > 9, and torch fp32 on the CPU within 1/4 of the bar (1e-5 of the scale) of
+    the float64 reference, for the forward, the input gradient and all six parameter gradients: the bar is not one the
+    reference itself strains."""
+    case = _wide_case(shape)
+    print(shape, case["counts"], [round(_share_of_bar(a, b), 4) for a, b in zip(case["cpu32"], case["want"])])
+    if shape[3] == "Tanh":
+        assert all(n >= 10 for n in case["counts"].values()), case["counts"]
+    for name, a, b in zip(_WIDE_NAMES, case["cpu32"], case["want"]):
+        assert _share_of_bar(a, b) <= 0.25, name
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("shape", [(s[0], tuple(s[1]), s[2], s[3]) for s in _MLP_SHAPES],
+                         ids=lambda s: f"{s[0]}-{s[1][0]}-{s[2]}-{s[3]}")
+def test_hipmlp3_wide_range_matches_float64(gpu_device, shape):
+    """The fused chain at the wide-range case (1000 rows, weights x 3, inputs over four decades) against the float64
+    nn.Sequential at 1e-5 of the scale: forward, input gradient and all six parameter gradients."""
+    case = _wide_case(shape)
+    if shape[3] == "Tanh":
+        assert all(n >= 10 for n in case["counts"].values()), case["counts"]
+    for name, a, b in zip(_WIDE_NAMES, case["cpu32"], case["want"]):
+        assert _share_of_bar(a, b) <= 0.25, f"{name}: torch fp32 on the CPU"
+    dev = torch.device(gpu_device)
+    import copy
+
+    fused = copy.deepcopy(case["fused"]).to(dev)
+    got = _run(fused, case["x"].to(dev), case["g"].to(dev))
+    shares = [_share_of_bar(a, b) for a, b in zip(got, case["want"])]
+    print(shape, case["counts"], [round(s, 4) for s in shares])
+    for name, s in zip(_WIDE_NAMES, shares):
+        assert s <= 1.0, f"{name}: {s:.3f} of the bar"
