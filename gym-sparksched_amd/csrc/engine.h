@@ -94,7 +94,12 @@ enum : int32_t { kPhPolicy = 0, kPhAction, kPhRoundCheck, kPhFulfill, kPhPop, kP
                  // observation sizes n, ne, levels, schedulable, then exec scores)
                  kPhDecParts,
                  // in-launch auto-resets (rollout_body): cycles, count
-                 kPhReset = kPhDecParts + 10, kCtReset, kNumPhases };
+                 kPhReset = kPhDecParts + 10, kCtReset,
+                 // the per-decision tail: completed decisions that fired no event (a round that continues), passes of
+                 // the schedulable predicate over the active list at the decision sites and in observe(), delta
+                 // observations
+                 kCtNoEvent, kCtPredPass, kCtDeltaObs, kNumPhases };
+static_assert(kNumPhases <= 64, "StateOffsets::sc_prof holds 64 sums");
 #ifdef SSIM_PROFILE
 #define SSIM_COUNT(ph) prof_add(ph, 1)
 #else
@@ -1751,6 +1756,61 @@ struct Sim {
   }
   __device__ __forceinline__ bool any_schedulable() { return scan_first(kScanAll, -1, source_job()) >= 0; }
 
+  // The per-decision tail. A decision point evaluates the schedulable predicate over the whole active
+  // list once: the scan that finds the decision (the end of simulate(), the round check of step_begin) keeps the
+  // ballot mask of every 64-node chunk in registers (SGPR pairs) and observe() takes them instead of evaluating
+  // stage_pred again on the state nothing has touched since. kPredChunks chunks (192 nodes) are kept; past them the
+  // scan only answers "any" and observe() recomputes. SSIM_TAIL_MASKS=0: observe() always recomputes.
+#ifndef SSIM_TAIL_MASKS
+#define SSIM_TAIL_MASKS 1
+#endif
+  // SSIM_TAIL_DELTA=0: every observation is written in full (observe()'s `delta`).
+#ifndef SSIM_TAIL_DELTA
+#define SSIM_TAIL_DELTA 1
+#endif
+  static constexpr int kPredChunks = 3;
+  uint64_t pred_m0 = 0, pred_m1 = 0, pred_m2 = 0;  // bit i & 63 of chunk i >> 6: node i is schedulable
+  bool pred_ok = false;  // the masks describe the current state (set by scan_sched, consumed by observe)
+  // "The arena rows of this env hold this episode's observation as of my last observe() in this launch": cleared when
+  // the engine is constructed (a launch's first observation is always full: the host owns the arena between launches)
+  // and by a reset, set by observe(). With it a round-continuing decision rewrites only what add_commitment can have
+  // changed. obs_ne: that observation's edge count.
+  bool obs_live = false;
+  int32_t obs_ne = 0;
+  __device__ __forceinline__ bool scan_sched(int src_job) {
+    SSIM_TIC(t0);
+    SSIM_COUNT(kCtPredPass);
+    const int n = h.n_active_stages;
+    const int16_t* act = H<int16_t>(O.active_stages);
+    const TopoView tv = topo_view();
+    uint64_t m0 = 0, m1 = 0, m2 = 0;
+    bool found = false;
+    for (int i0 = 0; i0 < n; i0 += W::kWidth) {
+      const int i = i0 + W::lane();
+      const int g = i < n ? act[i] : -1;
+      const uint64_t m = W::ballot(g >= 0 && stage_pred(g, kScanAll, -1, src_job, tv));
+      found = found || m != 0;
+      const int c = i0 >> 6;
+      if (!SSIM_TAIL_MASKS || c >= kPredChunks) {  // past the register masks only "any" is asked for
+        if (found) break;
+        continue;
+      }
+      const uint64_t b = m << (W::kWidth == 64 ? 0 : (i0 & 63));  // (a one-lane wave adds one bit per step)
+      if (c == 0)
+        m0 |= b;
+      else if (c == 1)
+        m1 |= b;
+      else
+        m2 |= b;
+    }
+    pred_m0 = m0;
+    pred_m1 = m1;
+    pred_m2 = m2;
+    pred_ok = SSIM_TAIL_MASKS && found && n <= 64 * kPredChunks;  // (found: the caller stops at this state)
+    SSIM_TOC(t0, kPhScan);
+    return found;
+  }
+
   __device__ __forceinline__ int find_backup(int e) {  // :821-845 (quirks Q1/Q2)
     const int jx = ex_job(e);
     check(jx >= 0);
@@ -2222,7 +2282,7 @@ struct Sim {
         SSIM_TOC(t_s, kPhPostScan);
         continue;
       }
-      const bool found = any_schedulable();
+      const bool found = scan_sched(source_job());
       if (!found) {
         release_idle_all(kPoolNone);
         h.source = kPoolNone;
@@ -2274,7 +2334,19 @@ struct Sim {
     else
       *p = v;
   }
-  __device__ __forceinline__ void observe(double reward) {
+  // step_done: the observation completes a step (the decision is counted in the same accumulator update). ncommit:
+  // committable() if the caller has it, else < 0. delta: the caller is a round-continuing decision, so with obs_live
+  // only the schedulable column and ranks, the schedulable list, the picks, the supplies and the scalar words are
+  // written; rem, recent duration, frontier, the row map, dag_ptr and the edges stand as this env's previous observe()
+  // left them (since then only add_commitment ran: com and sel of one stage, one job's supply, the source's cfrom).
+  __device__ __forceinline__ void observe(double reward, bool step_done = false, int ncommit = -1,
+                                          bool delta = false) {
+    const bool dl = SSIM_TAIL_DELTA && delta && obs_live;
+    const bool masks = SSIM_TAIL_MASKS && pred_ok;
+    pred_ok = false;
+    const uint64_t pm0 = pred_m0, pm1 = pred_m1, pm2 = pred_m2;
+    if (!masks) SSIM_COUNT(kCtPredPass);
+    if (dl) SSIM_COUNT(kCtDeltaObs);
     const int n = h.n_active_stages;
     const int src_job = source_job();
     const int16_t* act = H<int16_t>(O.active_stages);
@@ -2300,17 +2372,26 @@ struct Sim {
       const int i = i0 + W::lane();
       const bool ok = i < n;
       const int g = ok ? act[i] : -1;
-      const bool s = ok && stage_pred(g, kScanAll, -1, src_job, tv);
+      bool s;
+      if (masks) {  // the decision site's scan (scan_sched) on this very state
+        const uint64_t pm = i0 < 64 ? pm0 : i0 < 128 ? pm1 : pm2;
+        s = ok && ((pm >> (i & 63)) & 1) != 0;
+      } else {
+        s = ok && stage_pred(g, kScanAll, -1, src_job, tv);
+      }
       const uint64_t m = W::ballot(s);
       const int r = nsched + W::rank(m);
       if (ok) {
-        const StageRec sr = stage(g);
-        obs_st(nodes + 3 * i + 0, (float)sr.rem);
-        obs_st(nodes + 3 * i + 1, (float)recent()[g]);
+        StageRec sr{};
+        if (!dl || s) sr = stage(g);
+        if (!dl) {
+          obs_st(nodes + 3 * i + 0, (float)sr.rem);
+          obs_st(nodes + 3 * i + 1, (float)recent()[g]);
+          obs_st(front + i, (uint8_t)(sr.unmet == 0 ? 1 : 0));
+          row_of[g] = (int16_t)i;
+        }
         obs_st(nodes + 3 * i + 2, s ? 1.0f : 0.0f);
-        obs_st(front + i, (uint8_t)(sr.unmet == 0 ? 1 : 0));
         obs_st(srank + i, s ? r : -1);
-        row_of[g] = (int16_t)i;
         if (s) {
           sched[r] = (int16_t)g;
           W::amin(&job(sr.job).pick, (sr.unmet == 0 ? 0 : 0x10000) | r);
@@ -2330,23 +2411,25 @@ struct Sim {
       const bool ok = k < nj;
       const int j = ok ? aj[k] : -1;
       const JobRec jr = ok ? job(j) : JobRec{};
-      const int cnt = ok ? jr.nact : 0;
-      int total = 0;
-      const int ex = W::excl_scan(cnt, &total);
-      if (ok) {
-        obs_st(ptr + k, run + ex);
-        obs_st(sup + k, (int32_t)jr.supply);
+      if (!dl) {
+        const int cnt = ok ? jr.nact : 0;
+        int total = 0;
+        const int ex = W::excl_scan(cnt, &total);
+        if (ok) obs_st(ptr + k, run + ex);
+        run += total;
       }
+      if (ok) obs_st(sup + k, (int32_t)jr.supply);
       const uint64_t ms = W::ballot(ok && j == src_job);
       if (ms) src_idx = k0 + W::ffs(ms);
-      run += total;
     }
-    if (W::lane() == 0) obs_st(ptr + nj, run);
-    check(run == n);
+    if (!dl) {
+      if (W::lane() == 0) obs_st(ptr + nj, run);
+      check(run == n);
+    }
     // edges: (row(u), row(v)) for active u, child v active; order = node order, children ascending
     int64_t* links = reinterpret_cast<int64_t*>(obs + HP(ob_edge_links)) + (int64_t)eid * ecap * 2;
-    int ne = 0;
-    for (int i0 = 0; i0 < n; i0 += W::kWidth) {
+    int ne = dl ? obs_ne : 0;
+    for (int i0 = 0; !dl && i0 < n; i0 += W::kWidth) {
       const int i = i0 + W::lane();
       const bool ok = i < n;
       const int g = ok ? act[i] : -1;
@@ -2400,6 +2483,8 @@ struct Sim {
       ne += total;
     }
     if (ne > ecap) fail(SSIM_ERR_CAPACITY);
+    obs_live = true;
+    obs_ne = ne;
     h.n_sched = nsched;
     h.src_idx = src_idx;
     h.stage_idx_n = n + 1;
@@ -2408,12 +2493,13 @@ struct Sim {
     a.edges += ne;
     a.jobs += nj;
     a.events += h.step_events;
+    if (step_done) a.decisions += 1;  // a step completed: counted with the observation that completes it
     *H<EnvAcc>(O.acc) = a;
     int64_t* const acc = reinterpret_cast<int64_t*>(obs + HP(ob_acc)) + (int64_t)eid * kNumAcc;
     int32_t* const cnts = reinterpret_cast<int32_t*>(obs + HP(ob_counts)) + (int64_t)eid * SSIM_NUM_COUNTS;
     double* const rew = reinterpret_cast<double*>(obs + HP(ob_reward)) + eid;
     double* const wall = reinterpret_cast<double*>(obs + HP(ob_wall_time)) + eid;
-    const int ncommit = committable();
+    if (ncommit < 0) ncommit = committable();
     W::sync();
     if (W::lane() == 0) {
       acc[0] = a.nodes;
@@ -2464,10 +2550,6 @@ struct Sim {
   __device__ __forceinline__ bool idle() const { return h.terminated || frozen() || h.num_jobs == 0; }
   __device__ __forceinline__ EnvAcc& acc() const { return *H<EnvAcc>(O.acc); }
   __device__ __forceinline__ bool pending() const { return W::uni(acc().pending) != 0; }
-  __device__ __forceinline__ void count_decision() {  // a step completed (its observation is written)
-    UF<int64_t> d{&acc().decisions};
-    d = (int64_t)d + 1;
-  }
   // The end of a step from its simulation on: returns false if `stop` preempted it (pending, see EnvAcc).
   template <class Stop>
   __device__ __forceinline__ bool finish_step(double t0, const Stop& stop) {
@@ -2485,11 +2567,11 @@ struct Sim {
     const double reward = -jobtime(t0, h.decisions);
     h.terminated = (h.n_completed == h.num_jobs) ? 1 : 0;
     // step's `assert committable and schedulable_stages` (:212-215): simulate() stopped at a decision
-    // point (state untouched since) unless the queue ran dry
+    // point (state untouched since, so observe() takes the predicate masks of that scan) unless the queue ran dry
     if (!h.terminated) check(r == kSimDecision);
-    count_decision();  // before observe(), which publishes the accumulators to the obs arena
+    if (r != kSimDecision) pred_ok = false;
     SSIM_TIC(t_o);
-    observe(reward);
+    observe(reward, /*step_done=*/true);
     SSIM_TOC(t_o, kPhObserve);
     store_header();
     return true;
@@ -2534,8 +2616,12 @@ struct Sim {
       rejected = true;
       return false;
     }
+    // committable() is read once per decision and carried through the action check, the round check and observe():
+    // add_commitment(n, ...) takes exactly n from it (unless it froze the env: then it is read again)
+    int ncommit = 0;
     if (idx == -1) {
-      commit_leftovers();
+      commit_leftovers();  // (everything committable goes to the common pool: none is left)
+      if (frozen()) ncommit = committable();
     } else {
       if (idx >= h.n_sched) {
         write_err_only(SSIM_ERR_KEY);
@@ -2543,7 +2629,8 @@ struct Sim {
         return false;
       }
       const int g = ld(H<int16_t>(O.sched_list) + idx);
-      if (nx > committable()) {
+      ncommit = committable();
+      if (nx > ncommit) {
         write_err_only(SSIM_ERR_TOO_MANY);
         rejected = true;
         return false;
@@ -2552,6 +2639,7 @@ struct Sim {
       const int n = nx < d ? nx : d;  // _adjust_num_executors
       check(n > 0);
       add_commitment(n, stage_pool(g));
+      ncommit = frozen() ? committable() : ncommit - n;
       st_sel(g) = 1;
       if (h.n_selected <= NE) {
         if (W::lane() == 0) H<int16_t>(O.sel_list)[h.n_selected] = (int16_t)g;
@@ -2565,12 +2653,15 @@ struct Sim {
     h.step_events = 0;
     SSIM_TOC(t_act, kPhAction);
     SSIM_TIC(t_rc);
-    const bool round_continues = committable() > 0 && any_schedulable();
+#if defined(SSIM_PROFILE) || !defined(__HIP_DEVICE_COMPILE__)
+    check(ncommit == committable());  // (the carried value: checked in the host and profile builds)
+#endif
+    const bool round_continues = ncommit > 0 && scan_sched(source_job());
     SSIM_TOC(t_rc, kPhRoundCheck);
-    if (round_continues) {
-      count_decision();
+    if (round_continues) {  // no event fired: the state differs from the last observation by one add_commitment
+      SSIM_COUNT(kCtNoEvent);
       SSIM_TIC(t_o);
-      observe(0.0);
+      observe(0.0, /*step_done=*/true, ncommit, /*delta=*/true);
       SSIM_TOC(t_o, kPhObserve);
       store_header();
       return false;
@@ -2655,6 +2746,8 @@ struct Sim {
     const int32_t* tpl = reinterpret_cast<const int32_t*>(rec_base + kResetHeadBytes + 8 * (int64_t)JC);
     const int nj = rec->num_jobs;
     if (nj <= 0) return;
+    obs_live = false;  // a new episode: its first observation is written in full
+    pred_ok = false;
     const EnvHeader* prev = H<EnvHeader>(O.hdr);
     const int prev_episode = W::uni(prev->episode);
     if (W::uni(prev->num_jobs) > 0) {  // the previous episode ends here (accumulators persist, EnvAcc)

@@ -26,7 +26,11 @@ DEC_PHASES = ["(decima features)", "(decima policy)", "(decima sample copy)"]  #
 DEC_PARTS = ["[policy setup]", "[policy prep MLPs]", "[policy message passing]", "[policy DAG/global summaries]",
              "[policy stage scores]", "#nodes", "#edges", "#levels", "#schedulable", "[policy exec scores]"]
 RESET_SLOTS = ["(auto-resets)", "#auto-resets"]  # engine.h kPhReset, kCtReset
-NUM_SLOTS = 40 + NSTAMPS + len(DEC_PHASES) + len(DEC_PARTS) + len(RESET_SLOTS)  # engine.h kNumPhases
+# engine.h kCtNoEvent, kCtPredPass, kCtDeltaObs: the per-decision tail's counters
+TAIL_SLOTS = ["#no-event decisions", "#predicate passes", "#delta observations"]
+RESET_AT = 40 + NSTAMPS + len(DEC_PHASES) + len(DEC_PARTS)
+# engine.h kNumPhases (PROF_NUM_SLOTS: a library built from sources with another count, e.g. 61 before the tail's)
+NUM_SLOTS = int(os.environ.get("PROF_NUM_SLOTS", RESET_AT + len(RESET_SLOTS) + len(TAIL_SLOTS)))
 
 
 def build_prof():
@@ -110,9 +114,12 @@ def main():
                 print(f"  {name:24s} {v / dec:10.3f} per decision")
             else:
                 print(f"  {name:24s} {v / dec:10.1f} cycles/decision  {100 * v / top:5.1f}% of top-level")
-        rs = prof[:, NUM_SLOTS - 2:].cpu().numpy().astype(np.float64).sum(axis=0)
+        rs = prof[:, RESET_AT:RESET_AT + 2].cpu().numpy().astype(np.float64).sum(axis=0)
         print(f"  {'(auto-resets)':24s} {rs[0] / dec:10.1f} cycles/decision; {int(rs[1])} resets, "
               f"{rs[0] / max(rs[1], 1):.0f} cycles each")
+        tail = prof[:, RESET_AT + 2:RESET_AT + 2 + len(TAIL_SLOTS)].cpu().numpy().astype(np.float64).sum(axis=0)
+        for name, v in zip(TAIL_SLOTS, tail):
+            print(f"  {name:24s} {v / dec:10.3f} per decision")
         # per-wave wall clock of the launch from the realtime stamps (10 ns ticks)
         ent, loaded, loop_end, saved = st[:, 0], st[:, 1], st[:, 2], st[:, 3]
         t0 = ent.min()
@@ -129,6 +136,7 @@ def main():
         res[f"K{K}"] = {"decisions": dec, "events_per_decision": (e1 - e0) / dec,
                         "cycles_per_decision": {n: float(v / dec) for n, v in zip(PHASES, tot)},
                         "top_level_sum": float(top / dec), "loop_iterations": float(it / dec),
+                        "tail_counters_per_decision": {n: float(v / dec) for n, v in zip(TAIL_SLOTS, tail)},
                         "wave_timeline_us": wall}
     os.makedirs(os.path.join(REPO, "gpurun_out"), exist_ok=True)
     with open(os.path.join(REPO, "gpurun_out", "phase_profile.json"), "w") as f:
