@@ -134,6 +134,7 @@ using DecimaTimedArgs = std::conditional_t<kTimed, ssim_decima_timed, DecimaTime
 template <bool kHelp = false, bool kTimed = false, bool kGreedy = false>
 struct DecimaPolicy {
   static constexpr bool kTimedMode = kTimed;
+  static constexpr bool kLazyRows = false;  // the features and the samples are read from the arena rows at every decision
   const Params* P;
   const uint8_t* obs;
   DecimaRolloutArgs a;

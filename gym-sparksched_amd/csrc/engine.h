@@ -97,9 +97,9 @@ enum : int32_t { kPhPolicy = 0, kPhAction, kPhRoundCheck, kPhFulfill, kPhPop, kP
                  kPhReset = kPhDecParts + 10, kCtReset,
                  // the per-decision tail: completed decisions that fired no event (a round that continues), passes of
                  // the schedulable predicate over the active list at the decision sites and in observe(), delta
-                 // observations
-                 kCtNoEvent, kCtPredPass, kCtDeltaObs, kNumPhases };
-static_assert(kNumPhases <= 64, "StateOffsets::sc_prof holds 64 sums");
+                 // observations; lazy observations (decision part and scalar block only) and row flushes
+                 kCtNoEvent, kCtPredPass, kCtDeltaObs, kCtLazyObs, kCtRowFlush, kNumPhases };
+static_assert(kNumPhases <= 72, "StateOffsets::sc_prof holds 72 sums");
 #ifdef SSIM_PROFILE
 #define SSIM_COUNT(ph) prof_add(ph, 1)
 #else
@@ -251,9 +251,12 @@ inline void fill_hot_params(Params* p) {
 // kN / kJ / kS: executor count, job cap and stage cap as compile-time constants (0 = read from the layout at
 // run time). A fully specialised instantiation sees every section offset (hot block, scratch), loop bound
 // and table size as a constant, so LDS accesses use immediate offsets and no SGPRs hold offsets.
-template <class W, int kN = 0, int kJ = 0, int kS = 0>
+// kLazy: observe() writes the arena's row arrays once per launch (flush_rows) instead of at every decision: the fused
+// rollouts whose action driver reads only the hot block (rollout.h kLazyRows). Every other engine observes eagerly.
+template <class W, int kN = 0, int kJ = 0, int kS = 0, bool kLazy = false>
 struct Sim {
   using WT = W;
+  static constexpr bool kLazyObs = kLazy;
   const ssim_layout& L;
   const ssim_dataset& D;
   const ssim_config& C;
@@ -638,6 +641,7 @@ struct Sim {
   __device__ __forceinline__ UF<int16_t, 1> job_state(int j) const { return {&job(j).state}; }
   __device__ __forceinline__ UF<int32_t, 1> job_arr_dec(int j) const { return {&job(j).arr_dec}; }
   __device__ __forceinline__ UF<int32_t, 1> job_done_dec(int j) const { return {&job(j).done_dec}; }
+  __device__ __forceinline__ UF<int32_t, 1> job_edges(int j) const { return {&job(j).edges}; }
   __device__ __forceinline__ UF<double, 2> job_tarr(int j) const { return {&jtimes(j).tarr}; }
   __device__ __forceinline__ UF<double, 2> job_tdone(int j) const { return {&jtimes(j).tdone}; }
   // executors
@@ -2021,6 +2025,10 @@ struct Sim {
     const int32_t* const fwk = HP(ts_fw_keymask);
     const int32_t* const fwm = HP(ts_fw_maxlevel);
     const double* const rough = HP(ts_rough);
+    // the carried edge count (JobRec::edges): every stage of the job is active, so every edge of the template counts
+    const bool bits = topo_masks();
+    const uint64_t* const topo = bits ? HP(ts_topo) : nullptr;
+    int ec = 0;
     for (int k0 = 0; k0 <= n; k0 += W::kWidth) {  // stage records, pools of the job and its stages, active list
       const int k = k0 + W::lane();
       if (k <= n) {
@@ -2043,9 +2051,16 @@ struct Sim {
           stage(g) = r;
           recent()[g] = ldg(rough, ts);
           as[h.n_active_stages + k] = (int16_t)g;
+          if (bits) ec += __builtin_popcount((uint32_t)(ldg(topo, ts) >> 32));
         }
       }
     }
+    int etot = 0;
+    if (bits)
+      W::excl_scan(ec, &etot);
+    else
+      etot = ldu(HP(ts_child_base), tsb + n) - ldu(HP(ts_child_base), tsb);
+    job_edges(j) = etot;
     W::sync();
     h.n_active_jobs += 1;
     h.n_active_stages += n;
@@ -2076,6 +2091,7 @@ struct Sim {
     bool changed = false;
     if (topo_masks()) {
       uint32_t cm = (uint32_t)(ldu(HP(ts_topo), ts) >> 32);
+      job_edges(j) -= __builtin_popcount(cm);  // the stage left the active list: its out-edges leave the observation
       while (cm) {
         const int c = base + __builtin_ctz(cm);
         cm &= cm - 1;
@@ -2085,6 +2101,7 @@ struct Sim {
       return changed;
     }
     const int kb = ldu(HP(ts_child_base), ts), ke = ldu(HP(ts_child_base), ts + 1);
+    job_edges(j) -= ke - kb;
     for (int k = kb; k < ke; ++k) {
       const int c = base + ldu(HP(ts_children), k);
       st_unmet(c) -= 1;
@@ -2339,11 +2356,57 @@ struct Sim {
   // only the schedulable column and ranks, the schedulable list, the picks, the supplies and the scalar words are
   // written; rem, recent duration, frontier, the row map, dag_ptr and the edges stand as this env's previous observe()
   // left them (since then only add_commitment ran: com and sel of one stage, one job's supply, the source's cfrom).
+  //
+  // The observation has three parts (observe_parts). The decision part (kDec) is what the next action needs and the
+  // hot block keeps: the pick reset, the schedulable list and ranks, the picks, the source index, h.n_sched /
+  // h.src_idx / h.stage_idx_n and the EnvAcc update. The scalar block (with kDec) is lane 0's acc / counts / reward /
+  // wall time words of the arena, written at every decision. The row part (kRows) writes the arena's row arrays:
+  // nodes, frontier, sched_rank, the row map, dag_ptr, exec_supplies, edge_links. An eager engine runs all three at
+  // every decision. A lazy one (kLazyObs) runs the first two and marks the rows stale; flush_rows() then writes the
+  // row part once, in full, from the state the env's last decision part saw (the end of the launch: rollout.h).
+  //
+  // The carried edge count. The counts, the accumulators and the capacity check need the observation's edge count at
+  // every decision, the edge pass only writes the rows. Every child of an active stage is itself live (a stage
+  // completes only after all its parents), so the count is the number of DAG edges leaving active stages:
+  // JobRec::edges holds it per job (on_job_arrival adds the template's edges, stage_completed takes the completed
+  // stage's children away) and the job pass sums it. The invariant is the reference's, not proven here: wherever the
+  // edge pass runs, the host and profile builds check() its count against the carried one.
+#if defined(SSIM_PROFILE) || !defined(__HIP_DEVICE_COMPILE__)
+  static constexpr bool kCheckEdges = true;
+#else
+  static constexpr bool kCheckEdges = false;
+#endif
+  bool rows_stale = false;  // (lazy) the arena's row arrays are older than the env's last decision part
   __device__ __forceinline__ void observe(double reward, bool step_done = false, int ncommit = -1,
                                           bool delta = false) {
-    const bool dl = SSIM_TAIL_DELTA && delta && obs_live;
-    const bool masks = SSIM_TAIL_MASKS && pred_ok;
-    pred_ok = false;
+    if constexpr (kLazyObs) {
+      SSIM_COUNT(kCtLazyObs);
+      observe_parts<true, false>(reward, step_done, ncommit, delta);
+      rows_stale = true;
+    } else {
+      observe_parts<true, true>(reward, step_done, ncommit, delta);
+    }
+  }
+  // The deferred row part of a lazy engine, for an env that is neither frozen nor pending (their rows stay as the
+  // last flush left them: sparksched.h SSIM_ERR_PENDING). Header in registers, state untouched since the env's last
+  // observe().
+  __device__ __forceinline__ void flush_rows() {
+    if (!rows_stale || frozen() || pending()) return;
+    SSIM_TIC(t_o);
+    SSIM_COUNT(kCtRowFlush);
+    observe_parts<false, true>(0.0, false, -1, false);
+    SSIM_TOC(t_o, kPhObserve);
+    rows_stale = false;
+    if (kCheckEdges && frozen()) {  // the edge pass disagreed with the carried count: the host sees the env frozen
+      store_header();
+      write_err_only(0u);
+    }
+  }
+  template <bool kDec, bool kRows>
+  __device__ __forceinline__ void observe_parts(double reward, bool step_done, int ncommit, bool delta) {
+    const bool dl = kDec && SSIM_TAIL_DELTA && delta && obs_live;
+    const bool masks = kDec && SSIM_TAIL_MASKS && pred_ok;
+    if (kDec) pred_ok = false;
     const uint64_t pm0 = pred_m0, pm1 = pred_m1, pm2 = pred_m2;
     if (!masks) SSIM_COUNT(kCtPredPass);
     if (dl) SSIM_COUNT(kCtDeltaObs);
@@ -2362,11 +2425,11 @@ struct Sim {
     // contiguous in node order and ranks grow with node order, so the min is the first frontier stage,
     // else the first schedulable one.
     const int16_t* ajl = H<int16_t>(O.active_jobs);
-    for (int k0 = 0; k0 < h.n_active_jobs; k0 += W::kWidth) {
+    for (int k0 = 0; kDec && k0 < h.n_active_jobs; k0 += W::kWidth) {
       const int k = k0 + W::lane();
       if (k < h.n_active_jobs) job(ajl[k]).pick = 0x7FFFFFFF;
     }
-    W::sync();
+    if (kDec) W::sync();
     int nsched = 0;
     for (int i0 = 0; i0 < n; i0 += W::kWidth) {
       const int i = i0 + W::lane();
@@ -2383,16 +2446,18 @@ struct Sim {
       const int r = nsched + W::rank(m);
       if (ok) {
         StageRec sr{};
-        if (!dl || s) sr = stage(g);
-        if (!dl) {
+        if ((kRows && !dl) || (kDec && s)) sr = stage(g);
+        if (kRows && !dl) {
           obs_st(nodes + 3 * i + 0, (float)sr.rem);
           obs_st(nodes + 3 * i + 1, (float)recent()[g]);
           obs_st(front + i, (uint8_t)(sr.unmet == 0 ? 1 : 0));
           row_of[g] = (int16_t)i;
         }
-        obs_st(nodes + 3 * i + 2, s ? 1.0f : 0.0f);
-        obs_st(srank + i, s ? r : -1);
-        if (s) {
+        if (kRows) {
+          obs_st(nodes + 3 * i + 2, s ? 1.0f : 0.0f);
+          obs_st(srank + i, s ? r : -1);
+        }
+        if (kDec && s) {
           sched[r] = (int16_t)g;
           W::amin(&job(sr.job).pick, (sr.unmet == 0 ? 0 : 0x10000) | r);
         }
@@ -2406,30 +2471,38 @@ struct Sim {
     int32_t* ptr = reinterpret_cast<int32_t*>(obs + HP(ob_dag_ptr)) + (int64_t)eid * (JC + 1);
     int32_t* sup = reinterpret_cast<int32_t*>(obs + HP(ob_supplies)) + (int64_t)eid * JC;
     int src_idx = nj, run = 0;
+    int ne_carried = 0;  // the sum of JobRec::edges (summed where the edge pass does not run, or is checked)
     for (int k0 = 0; k0 < nj; k0 += W::kWidth) {
       const int k = k0 + W::lane();
       const bool ok = k < nj;
       const int j = ok ? aj[k] : -1;
       const JobRec jr = ok ? job(j) : JobRec{};
-      if (!dl) {
+      if (kRows && !dl) {
         const int cnt = ok ? jr.nact : 0;
         int total = 0;
         const int ex = W::excl_scan(cnt, &total);
         if (ok) obs_st(ptr + k, run + ex);
         run += total;
       }
-      if (ok) obs_st(sup + k, (int32_t)jr.supply);
-      const uint64_t ms = W::ballot(ok && j == src_job);
-      if (ms) src_idx = k0 + W::ffs(ms);
+      if ((!kRows || kCheckEdges) && !dl) {
+        int total = 0;
+        W::excl_scan(ok ? (int)jr.edges : 0, &total);
+        ne_carried += total;
+      }
+      if (kRows && ok) obs_st(sup + k, (int32_t)jr.supply);
+      if (kDec) {
+        const uint64_t ms = W::ballot(ok && j == src_job);
+        if (ms) src_idx = k0 + W::ffs(ms);
+      }
     }
-    if (!dl) {
+    if (kRows && !dl) {
       if (W::lane() == 0) obs_st(ptr + nj, run);
       check(run == n);
     }
     // edges: (row(u), row(v)) for active u, child v active; order = node order, children ascending
     int64_t* links = reinterpret_cast<int64_t*>(obs + HP(ob_edge_links)) + (int64_t)eid * ecap * 2;
-    int ne = dl ? obs_ne : 0;
-    for (int i0 = 0; !dl && i0 < n; i0 += W::kWidth) {
+    int ne = dl ? obs_ne : kRows ? 0 : ne_carried;
+    for (int i0 = 0; kRows && !dl && i0 < n; i0 += W::kWidth) {
       const int i = i0 + W::lane();
       const bool ok = i < n;
       const int g = ok ? act[i] : -1;
@@ -2482,6 +2555,11 @@ struct Sim {
       }
       ne += total;
     }
+    if constexpr (kRows && kCheckEdges) {  // the edge pass's count against the carried one
+      if (!dl) check(ne == (kDec ? ne_carried : obs_ne));
+      if (!kDec) check(ne == ne_carried);
+    }
+    if constexpr (!kDec) return;  // (flush_rows: the decision part and the scalar block stand)
     if (ne > ecap) fail(SSIM_ERR_CAPACITY);
     obs_live = true;
     obs_ne = ne;

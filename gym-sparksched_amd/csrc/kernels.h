@@ -134,7 +134,8 @@ __device__ __forceinline__ void rollout_body(const Params* __restrict__ P, uint8
 #ifdef SSIM_PROFILE
   const uint64_t rt_entry = WaveHip::realtime();
 #endif
-  Sim<WaveHip, kN, kJ, kS> s(P, state, g_smem, obs, eid, kRes, row_cold, ex_lds && !kRes);
+  using SimT = Sim<WaveHip, kN, kJ, kS, Pol::kLazyRows>;  // (lazy arena rows: the driver's choice, rollout.h)
+  SimT s(P, state, g_smem, obs, eid, kRes, row_cold, ex_lds && !kRes);
 #ifdef SSIM_PROFILE
   s.prof_set(kTCtor, WaveHip::realtime());
 #endif
@@ -143,7 +144,7 @@ __device__ __forceinline__ void rollout_body(const Params* __restrict__ P, uint8
   s.prof_set(kTEntry, rt_entry);
   s.prof_set(kTLoaded, WaveHip::realtime());
 #endif
-  const auto reset_in_place = [&](Sim<WaveHip, kN, kJ, kS>& x) {
+  const auto reset_in_place = [&](SimT& x) {
     if constexpr (Pol::kTimedMode)
       pol.reset_episode(x, rec);  // reseeded, from the env's reset schedule (decima_rollout.h)
     else

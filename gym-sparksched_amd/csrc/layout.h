@@ -79,7 +79,7 @@ struct JobRec {
   int16_t sat, local, supply, state; // saturated count, |local_executors|, exec supply, 0/1/2
   int32_t arr_dec, done_dec;         // decision counter at arrival / completion (reward union)
   int32_t pick;  // heuristics find_stage of the job at the last observation (packed min key, engine.h observe)
-  int32_t pad;
+  int32_t edges;  // observation edges leaving the job's active stages (engine.h "carried edge count")
 };
 static_assert(sizeof(JobRec) == 32, "job record");
 
@@ -158,7 +158,7 @@ struct StateOffsets {
       sched_list;
   int64_t st_recent /*cold f64[S]*/, pool_tab /*cold uint8 [P][set_cap]*/, row_of /*cold int16[S]*/;
   int64_t sc_execs /*ExecRec[N], HBM-resident step / rollout kernels (Sim ex_lds)*/, sc_keys_a, sc_keys_b /*int32[N+1]*/, sc_plan /*int32[2C]*/, sc_tab_a, sc_tab_b, sc_tab_p /*uint8[set_cap]*/,
-      sc_dcache /*uint32[N][24] when N <= kDurCacheMaxExecs*/, sc_bits /*uint32[4]*/, sc_prof /*uint64[64], diagnostic -DSSIM_PROFILE build
+      sc_dcache /*uint32[N][24] when N <= kDurCacheMaxExecs*/, sc_bits /*uint32[4]*/, sc_prof /*uint64[72], diagnostic -DSSIM_PROFILE build
       only*/, sc_row_of /*int16[S], last: LDS-resident kernels only*/;
   int64_t scratch_hbm_bytes;  // the scratch without sc_row_of: what an HBM-resident kernel allocates
 };
@@ -242,7 +242,7 @@ constexpr StateOffsets state_offsets(int64_t N, int64_t J, int64_t S) {
   s = align16(s + (T > 64 && T <= kPagedTabMax ? 16 : 0));
   O.sc_prof = s;
 #ifdef SSIM_PROFILE
-  s += 8 * 64;
+  s += 8 * 72;
 #endif
   O.scratch_hbm_bytes = align16(s);
   O.sc_row_of = O.scratch_hbm_bytes;

@@ -21,6 +21,9 @@ struct NoBudget : NoStop {
 // act() chose (the env is then frozen with SSIM_ERR_INVARIANT).
 struct HeuristicPolicy {  // fair / FIFO / random (policy.h)
   static constexpr bool kTimedMode = false;  // (fixed-duration collection: decima_rollout.h DecimaPolicy)
+  // act() reads only the hot block (picks, schedulable list, header), never the arena's row arrays: the engine of
+  // this driver's rollouts writes them once per launch (Sim kLazyObs, rollout_loop's exit)
+  static constexpr bool kLazyRows = true;
   int kind;
   uint64_t seed;
   // whether act() would choose an action (checked before a budget claim, so a claim is never spent on an env whose
@@ -44,6 +47,7 @@ struct HeuristicPolicy {  // fair / FIFO / random (policy.h)
 // so the tuned k_rollout instantiations carry none of its code.
 struct PrioPolicy {
   static constexpr bool kTimedMode = false;
+  static constexpr bool kLazyRows = true;  // (as HeuristicPolicy: sim_policy_prio reads the hot block only)
   int kind;
   template <class S>
   __device__ __forceinline__ bool can_act(const S&) const {
@@ -67,7 +71,9 @@ struct RolloutCursor {
   int64_t last;      // the budget counter at the wave's previous claim
 };
 // The decision loop of a fused rollout on engine `s` (any residency). `reset_env(s)` resets a finished episode in
-// place.
+// place. Every way out of the loop is a break to its one exit point, where a lazy engine (Sim kLazyObs) writes the
+// arena rows its decisions deferred: at each such break the state is as the env's last observation saw it, or the
+// env is frozen or pending (flush_rows skips those).
 template <class SimT, class Pol, class StopT, class ResetFn>
 __device__ __forceinline__ void rollout_loop(SimT& s, const Pol& pol, const StopT& stop, RolloutCursor& c, int B,
                                             int eid, int num_steps, bool autoreset, int32_t* action_log,
@@ -157,6 +163,7 @@ __device__ __forceinline__ void rollout_loop(SimT& s, const Pol& pol, const Stop
     }
 #endif
   }
+  if constexpr (SimT::kLazyObs) s.flush_rows();
 }
 
 }  // namespace ssim

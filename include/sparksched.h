@@ -30,9 +30,14 @@ extern "C" {
 #define SSIM_ERR_SPACE 0x1u       /* ValueError: action not in action space (spark_sched_sim.py:276-277) */
 #define SSIM_ERR_KEY 0x2u         /* KeyError: stage_idx >= #schedulable stages (spark_sched_sim.py:284) */
 #define SSIM_ERR_TOO_MANY 0x4u    /* ValueError: num_exec > committable executors (:294-295) */
-#define SSIM_ERR_PENDING 0x8u     /* the env's last step was preempted mid-simulation (SSIM_ROLLOUT_PREEMPT); the obs
-                                     arena still holds the previous observation; any ssim_rollout_* call or
-                                     ssim_step completes it (ssim_step then ignores its action for that env) */
+#define SSIM_ERR_PENDING 0x8u     /* the env's last step was preempted mid-simulation (SSIM_ROLLOUT_PREEMPT); any
+                                     ssim_rollout_* call or ssim_step completes it (ssim_step then ignores its action
+                                     for that env). Until then the env's scalar words (acc, counts, reward, wall_time)
+                                     are those of its last completed decision, and its row arrays (nodes, frontier,
+                                     sched_rank, dag_ptr, exec_supplies, edge_links) are unspecified: a fused rollout
+                                     of a heuristic or priority kind writes an env's rows once, when the env leaves
+                                     the launch with no step pending. A frozen env's rows (SSIM_ERR_STICKY) are
+                                     likewise whatever the last launch that left it unfrozen wrote. */
 #define SSIM_ERR_INVARIANT 0x10u  /* an `assert` of the reference fired; env frozen */
 #define SSIM_ERR_CAPACITY 0x20u   /* a device capacity (commitments, trace) overflowed; env frozen */
 #define SSIM_ERR_SAMPLER 0x40u    /* task_duration found no durations (reference raises); env frozen */

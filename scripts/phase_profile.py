@@ -26,8 +26,8 @@ DEC_PHASES = ["(decima features)", "(decima policy)", "(decima sample copy)"]  #
 DEC_PARTS = ["[policy setup]", "[policy prep MLPs]", "[policy message passing]", "[policy DAG/global summaries]",
              "[policy stage scores]", "#nodes", "#edges", "#levels", "#schedulable", "[policy exec scores]"]
 RESET_SLOTS = ["(auto-resets)", "#auto-resets"]  # engine.h kPhReset, kCtReset
-# engine.h kCtNoEvent, kCtPredPass, kCtDeltaObs: the per-decision tail's counters
-TAIL_SLOTS = ["#no-event decisions", "#predicate passes", "#delta observations"]
+# engine.h kCtNoEvent, kCtPredPass, kCtDeltaObs, kCtLazyObs, kCtRowFlush: the per-decision tail's counters
+TAIL_SLOTS = ["#no-event decisions", "#predicate passes", "#delta observations", "#lazy observations", "#row flushes"]
 RESET_AT = 40 + NSTAMPS + len(DEC_PHASES) + len(DEC_PARTS)
 # engine.h kNumPhases (PROF_NUM_SLOTS: a library built from sources with another count, e.g. 61 before the tail's)
 NUM_SLOTS = int(os.environ.get("PROF_NUM_SLOTS", RESET_AT + len(RESET_SLOTS) + len(TAIL_SLOTS)))
