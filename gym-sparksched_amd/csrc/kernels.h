@@ -193,6 +193,15 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, 64), amdgpu_waves_per_e
   rollout_body<kRes, 0, 0, 0, PrioPolicy>(P, state, obs, PrioPolicy{kind}, num_steps, flags, limits, reset, action_log,
                                           prof_out, budget, env_steps);
 }
+// The rollout of the weighted-fair kinds (SSIM_POLICY_WFAIR_BASE ..; rollout.h WfairPolicy): as k_rollout_prio, a third
+// action driver under its own symbol for the two run-time-shape engines (k_wfair_lds.hip, k_wfair_hbm.hip, the flags of
+// their k_prio_* siblings), so k_rollout_prio's instantiations are compiled from the code they had before.
+template <bool kRes>
+__global__ __attribute__((amdgpu_flat_work_group_size(1, 64), amdgpu_waves_per_eu(SSIM_ROLLOUT_WAVES(kRes)))) void k_rollout_wfair(SSIM_ROLLOUT_ARGS) {
+  (void)seed;
+  rollout_body<kRes, 0, 0, 0, WfairPolicy>(P, state, obs, WfairPolicy{kind}, num_steps, flags, limits, reset,
+                                           action_log, prof_out, budget, env_steps);
+}
 
 // Test hook (ssim_debug_set_trace_ex, tests/test_gpu_sets.py): a trace of CPython-set operations on one pool (job 0's)
 // of env 0 through the set code of the engine instantiation `Sim<WV, kN, kJ, kS>` with residency kRes — the template
@@ -268,3 +277,6 @@ KernelSet kernels_hbm_n50();   // k_hbm_n50.hip: hot block in HBM, 50 executors 
 // the priority kinds' rollout (k_rollout_prio), one per residency
 RolloutFn rollout_prio_lds();  // k_prio_lds.hip: LDS-resident, any shape
 RolloutFn rollout_prio_hbm();  // k_prio_hbm.hip: hot block in HBM, any shape
+// the weighted-fair kinds' rollout (k_rollout_wfair), one per residency
+RolloutFn rollout_wfair_lds();  // k_wfair_lds.hip: LDS-resident, any shape
+RolloutFn rollout_wfair_hbm();  // k_wfair_hbm.hip: hot block in HBM, any shape

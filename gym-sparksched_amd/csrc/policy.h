@@ -14,6 +14,10 @@
 //                 (prio_cp_stage; ties to the lowest row). Their own driver (prio_act / sim_policy_prio) and their own
 //                 rollout kernel (kernels.h k_rollout_prio): policy_act is inlined into every tuned k_rollout
 //                 instantiation and stays as it is. DESIGN.md "Priority schedulers".
+//   WFair(alpha): weighted fair (wfair_act), kinds SSIM_POLICY_WFAIR_BASE + (2 alpha + 4): fair's rule with a per-job
+//                 cap min(N, ceil(N * W(k)^alpha / sum of W^alpha)), alpha a half-integer in [-2, 2]. Its own
+//                 driver and rollout kernel (rollout.h WfairPolicy, kernels.h k_rollout_wfair), so k_rollout_prio is
+//                 compiled from the code it had without these kinds. DESIGN.md "Weighted-fair schedulers".
 #pragma once
 #include <stdint.h>
 
@@ -106,8 +110,11 @@ __device__ __forceinline__ StepIn policy_act(int kind, uint64_t seed, uint64_t c
 }
 
 // ---------------------------------------------------------------------------------- SJF / SJF-CP (priority kinds)
+// The kinds that are not policy_act's: SJF / SJF-CP and weighted fair (prio_act takes all of them; on the device the
+// rollouts of weighted fair have their own driver, in the one-lane host build PrioPolicy drives them too).
 __device__ __forceinline__ bool policy_is_prio(int kind) {
-  return kind == SSIM_POLICY_SJF || kind == SSIM_POLICY_SJF_CP;
+  return kind == SSIM_POLICY_SJF || kind == SSIM_POLICY_SJF_CP ||
+         (kind >= SSIM_POLICY_WFAIR_BASE && kind <= SSIM_POLICY_WFAIR_LAST);
 }
 constexpr int kPrioMaxStages = 64;  // SJF-CP: one lane (one bit of a child set) per row of the chosen job
 
@@ -217,6 +224,161 @@ __device__ __forceinline__ int prio_cp_stage(int n, Row row) {
   }
 }
 
+// ------------------------------------------------------------------------------------- weighted fair (WFair(alpha))
+// The kinds SSIM_POLICY_WFAIR_BASE + (alpha2 + 4), alpha2 = 2 * alpha in -4..4 (include/sparksched.h has the rule; the
+// host scheduler WeightedFairScheduler is its specification). Every written operation below is one correctly rounded
+// float64 operation and none may be fused with a neighbour (a * b + c contracted to an fma rounds once, not twice), so
+// the functions that hold them switch contraction off.
+#if defined(__clang__)
+#define SSIM_FP_NO_CONTRACT _Pragma("clang fp contract(off)")
+#else
+#define SSIM_FP_NO_CONTRACT  // (the host build compiles with -ffp-contract=off)
+#endif
+__device__ __forceinline__ bool policy_is_wfair(int kind) {
+  return kind >= SSIM_POLICY_WFAIR_BASE && kind <= SSIM_POLICY_WFAIR_LAST;
+}
+__device__ __forceinline__ int wfair_alpha2(int kind) { return kind - SSIM_POLICY_WFAIR_BASE - 4; }
+constexpr int kWfairKeep = 4;  // blocks of 64 jobs whose weights stay in registers between the two passes
+
+// p = W^(alpha2 / 2) from multiplies, one square root and one divide; a job without work weighs 1 under alpha2 = 0
+// (every job does), else 0. alpha2 is wave-uniform.
+__device__ __forceinline__ double wfair_weight(double w, int alpha2) {
+  SSIM_FP_NO_CONTRACT
+  if (!(w > 0.0)) return alpha2 == 0 ? 1.0 : 0.0;
+  const int a = alpha2 < 0 ? -alpha2 : alpha2;
+  double h = 1.0;
+  if (a == 1)
+    h = __builtin_sqrt(w);
+  else if (a == 2)
+    h = w;
+  else if (a == 3)
+    h = w * __builtin_sqrt(w);
+  else if (a == 4)
+    h = w * w;
+  return alpha2 < 0 ? 1.0 / h : h;
+}
+
+// The sum of one block of 64 weights, folding halves: x[:32] + x[32:], then 16, 8, 4, 2, 1. On a wave that is the
+// xor-32 .. xor-1 butterfly (WaveHip::sum_d's association); the one-lane build folds a local array.
+template <class W>
+__device__ __forceinline__ double wfair_block_sum(double x) {
+  SSIM_FP_NO_CONTRACT
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) x = x + W::shfl_xor_d(x, off);
+  return W::uni(x);
+}
+__device__ __forceinline__ double wfair_fold64(double* x) {
+  SSIM_FP_NO_CONTRACT
+  for (int half = 32; half > 0; half >>= 1)
+    for (int i = 0; i < half; ++i) x[i] = x[i] + x[i + half];
+  return x[0];
+}
+
+// P: the block sums of weight(k), k < nj, added left to right from 0.0. keep[b] receives this lane's weight of block
+// b < kWfairKeep (0.0 past nj) for the second pass.
+template <class W, class Weight>
+__device__ __forceinline__ double wfair_total(int nj, Weight weight, double (&keep)[kWfairKeep]) {
+  SSIM_FP_NO_CONTRACT
+  double P = 0.0;
+  if constexpr (W::kWidth == 64) {
+    const int l = W::lane();
+#pragma unroll
+    for (int b = 0; b < kWfairKeep; ++b) {
+      keep[b] = 0.0;
+      if (b * 64 < nj) {
+        if (b * 64 + l < nj) keep[b] = weight(b * 64 + l);
+        P = P + wfair_block_sum<W>(keep[b]);
+      }
+    }
+    for (int k0 = kWfairKeep * 64; k0 < nj; k0 += 64) {
+      double x = 0.0;
+      if (k0 + l < nj) x = weight(k0 + l);
+      P = P + wfair_block_sum<W>(x);
+    }
+  } else {
+    for (int b = 0; b < kWfairKeep; ++b) keep[b] = 0.0;
+    for (int k0 = 0; k0 < nj; k0 += 64) {
+      double x[64];
+      for (int i = 0; i < 64; ++i) x[i] = k0 + i < nj ? weight(k0 + i) : 0.0;
+      P = P + wfair_fold64(x);
+    }
+  }
+  return P;
+}
+
+// cap = min(N, ceil((N * p) / P)), P > 0
+__device__ __forceinline__ int wfair_cap(int N, double p, double P) {
+  SSIM_FP_NO_CONTRACT
+  const double c = __builtin_ceil(((double)N * p) / P);
+  return c < (double)N ? (int)c : N;
+}
+
+// The rule over a per-active-job view (policy_act's, plus work(k) = W(k), prio_job's): the source job keeps every
+// committable executor if it has a pick; else one lane per job, 64 jobs per round, each lane forms its job's weight, a
+// butterfly per block gives P, and a second pass over the blocks finds the first job other than the source under its
+// cap with a pick (ballot, ffs) and broadcasts its pick and room. Wave-uniform control flow around every cross-lane
+// operation; the weights of the first kWfairKeep blocks are not computed twice.
+template <class W, class Work, class Pick, class Supply>
+__device__ __forceinline__ StepIn wfair_act(int alpha2, int N, int nj, int comm, int src, Work work, Pick pick,
+                                            Supply supply) {
+  StepIn a;
+  a.stage_idx = -1;
+  a.num_exec = comm > 0 ? comm : 1;
+  if (src < nj) {
+    const int s = W::uni(pick(src));
+    if (s >= 0) {
+      a.stage_idx = s;
+      return a;
+    }
+  }
+  const auto weight = [&](int k) { return wfair_weight(work(k), alpha2); };
+  double keep[kWfairKeep];
+  const double P = wfair_total<W>(nj, weight, keep);
+  if (!(P > 0.0)) return a;
+  if constexpr (W::kWidth == 64) {
+    const int l = W::lane();
+    const auto block = [&](int k0, double p) {
+      const int k = k0 + l;
+      int cap = 0, sup = 0, s = -1;
+      if (k < nj && k != src) {
+        cap = wfair_cap(N, p, P);
+        sup = supply(k);
+        if (sup < cap) s = pick(k);
+      }
+      const uint64_t m = W::ballot(s >= 0);
+      if (m == 0) return false;
+      const int at = W::ffs(m);
+      a.stage_idx = W::bcast_i(s, at);
+      const int room = W::bcast_i(cap - sup, at);
+      a.num_exec = comm < room ? comm : room;
+      return true;
+    };
+#pragma unroll
+    for (int b = 0; b < kWfairKeep; ++b) {
+      if (b * 64 >= nj) return a;
+      if (block(b * 64, keep[b])) return a;
+    }
+    for (int k0 = kWfairKeep * 64; k0 < nj; k0 += 64) {
+      double p = 0.0;
+      if (k0 + l < nj) p = weight(k0 + l);
+      if (block(k0, p)) return a;
+    }
+  } else {
+    for (int k = 0; k < nj; ++k) {
+      if (k == src) continue;
+      const int cap = wfair_cap(N, weight(k), P), sup = supply(k);
+      if (sup >= cap) continue;
+      const int s = pick(k);
+      if (s >= 0) {
+        a.stage_idx = s;
+        a.num_exec = comm < cap - sup ? comm : cap - sup;
+        return a;
+      }
+    }
+  }
+  return a;
+}
+
 template <class W>
 struct PolicyView {
   const ssim_layout& L;
@@ -259,8 +421,27 @@ struct PolicyView {
     return reinterpret_cast<const int64_t*>(obs + L.ob_edge_links) + (int64_t)eid * L.edge_cap * 2;
   }
 
-  // SJF / SJF-CP on the observation (the rule at the top of this file, the specification's own arrays)
+  // Weighted fair on the observation: W(k) over the job's rows in row order, find_stage, ob_supplies
+  __device__ __forceinline__ StepIn wfair(int kind) const {
+    const int32_t* c = counts();
+    const int32_t* p = ptr();
+    const int32_t* su = sup();
+    const float* nd = nodes();
+    return wfair_act<W>(
+        wfair_alpha2(kind), L.num_executors, W::uni(c[SSIM_OC_NUM_JOBS]), W::uni(c[SSIM_OC_COMMITTABLE]),
+        W::uni(c[SSIM_OC_SOURCE_JOB_IDX]),
+        [&](int k) {
+          double sum = 0.0;
+          for (int r = p[k]; r < p[k + 1]; ++r) sum += (double)nd[3 * r] * (double)nd[3 * r + 1];
+          return sum;
+        },
+        [&](int k) { return find_stage(k); }, [&](int k) { return su[k]; });
+  }
+
+  // SJF / SJF-CP on the observation (the rule at the top of this file, the specification's own arrays); the
+  // weighted-fair kinds share the entry
   __device__ __forceinline__ StepIn prio_act(int kind) const {
+    if (policy_is_wfair(kind)) return wfair(kind);
     const int32_t* c = counts();
     const int32_t* p = ptr();
     const float* nd = nodes();
@@ -343,6 +524,31 @@ __device__ __forceinline__ StepIn sim_policy_legacy(SimT& s, int kind, uint64_t 
 // local stage ids, a completed stage standing for no row. Children come from the dataset's topology (the bit sets of
 // templates of <= 32 stages, else the child lists) with observe()'s liveness test; the schedulable rows and their ranks
 // from the schedulable list observe() wrote (ascending stage index: one job's entries are contiguous).
+// Weighted fair from the hot block: PolicyView::wfair's rule on the stage records (W(k) as sim_policy_prio's, over all
+// of the job's stage records), the picks and supplies of the job records, the header's source job.
+template <class SimT>
+__device__ __forceinline__ StepIn sim_policy_wfair(SimT& s, int kind) {
+  using W = typename SimT::WT;
+  const int16_t* aj = s.template H<int16_t>(s.O.active_jobs);
+  const double* recent = s.recent();
+  return wfair_act<W>(
+      wfair_alpha2(kind), s.NE, s.h.n_active_jobs, s.committable(), s.h.src_idx,
+      [&](int k) {
+        const JobRec jr = s.job(aj[k]);
+        double sum = 0.0;
+        for (int g = jr.base; g < jr.base + jr.nst; ++g) {
+          const StageRec sr = s.stage(g);
+          sum += (double)(float)sr.rem * (double)(float)recent[g];
+        }
+        return sum;
+      },
+      [&](int k) {
+        const int key = s.job(aj[k]).pick;
+        return key == 0x7FFFFFFF ? -1 : (key & 0xFFFF);
+      },
+      [&](int k) { return (int)s.job(aj[k]).supply; });
+}
+
 template <class SimT>
 __device__ __forceinline__ StepIn sim_policy_prio(SimT& s, int kind) {
   using W = typename SimT::WT;
@@ -415,6 +621,7 @@ __device__ __forceinline__ StepIn sim_policy_prio(SimT& s, int kind) {
 // Any kind, from the hot block (the host build's rollout loop; the device kernels call the driver of their family).
 template <class SimT>
 __device__ __forceinline__ StepIn sim_policy(SimT& s, int kind, uint64_t seed) {
+  if (policy_is_wfair(kind)) return sim_policy_wfair(s, kind);
   return policy_is_prio(kind) ? sim_policy_prio(s, kind) : sim_policy_legacy(s, kind, seed);
 }
 

@@ -55,7 +55,37 @@ struct PrioPolicy {
   }
   template <class S>
   __device__ __forceinline__ bool act(S& s, int /*k*/, StepIn* a) const {
+    // (the one-lane host build drives every kind of policy_is_prio through this driver, weighted fair included; a
+    // device launch of those kinds runs WfairPolicy, and k_rollout_prio holds none of their code)
+    if constexpr (S::WT::kWidth == 1) {
+      if (policy_is_wfair(kind)) {
+        *a = sim_policy_wfair(s, kind);
+        return true;
+      }
+    }
     *a = sim_policy_prio(s, kind);
+    return true;
+  }
+  template <class S>
+  __device__ __forceinline__ void done(S&) const {}
+  template <class S>
+  __device__ __forceinline__ void rejected(S&) const {}
+};
+
+// Weighted fair (policy.h sim_policy_wfair): the action driver of k_rollout_wfair (kernels.h), apart from PrioPolicy so
+// that k_rollout_prio is compiled from the code it had before these kinds existed (measured: DESIGN.md "Weighted-fair
+// schedulers").
+struct WfairPolicy {
+  static constexpr bool kTimedMode = false;
+  static constexpr bool kLazyRows = true;  // (sim_policy_wfair reads the hot block only)
+  int kind;
+  template <class S>
+  __device__ __forceinline__ bool can_act(const S&) const {
+    return true;
+  }
+  template <class S>
+  __device__ __forceinline__ bool act(S& s, int /*k*/, StepIn* a) const {
+    *a = sim_policy_wfair(s, kind);
     return true;
   }
   template <class S>

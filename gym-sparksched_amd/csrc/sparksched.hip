@@ -5,9 +5,9 @@
 // temporary CPython-set tables, commitment plan) lives in LDS. Kernels:
 //   k_reset   : env init from a host-sampled job sequence + _load_initial_jobs + first observation
 //   k_step    : one env.step per env from device action arrays (obs written to the obs arena)
-//   k_policy  : device action driver (fair / FIFO / random / SJF / SJF-CP) reading the obs arena
+//   k_policy  : device action driver (fair / FIFO / random / SJF / SJF-CP / weighted fair) reading the obs arena
 //   k_rollout : `num_steps` x (policy -> step) fused into one launch (no host round trips); k_rollout_prio for the
-//               SJF / SJF-CP kinds
+//               SJF / SJF-CP kinds, k_rollout_wfair for the weighted-fair kinds
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
 #include <stdlib.h>
@@ -55,6 +55,19 @@ __global__ __launch_bounds__(64) void k_policy(const Params* __restrict__ P, con
     stage_idx[eid] = a.stage_idx;
     num_exec[eid] = a.num_exec;
   }
+}
+
+// ssim_debug_wfair: the weighted-fair weight, sum and cap of policy.h on given job works, one wave
+__global__ __launch_bounds__(64) void k_debug_wfair(const double* __restrict__ Wk, int n, int alpha2, int N, double* p,
+                                                    double* P, int32_t* cap) {
+  double keep[kWfairKeep];
+  const double tot = wfair_total<WaveHip>(n, [&](int k) { return wfair_weight(Wk[k], alpha2); }, keep);
+  for (int k = WaveHip::lane(); k < n; k += 64) {
+    const double pk = wfair_weight(Wk[k], alpha2);
+    p[k] = pk;
+    cap[k] = tot > 0.0 ? wfair_cap(N, pk, tot) : 0;
+  }
+  if (WaveHip::lane() == 0) *P = tot;
 }
 
 __global__ __launch_bounds__(64) void k_decima(const Params* __restrict__ P, const uint8_t* obs, float nts,
@@ -192,13 +205,19 @@ static const DecimaUnitRow& pick_decima(const Params& p) {
   static const Table t;
   return t.row[unit_of(p, decima_unit)];
 }
-// The priority kinds (SJF / SJF-CP) run k_rollout_prio, which exists for the two run-time-shape engines only.
+// The priority kinds (SJF / SJF-CP) run k_rollout_prio, which exists for the two run-time-shape engines only; the
+// weighted-fair kinds k_rollout_wfair, likewise.
 static bool prio_kind(int32_t kind) { return kind == SSIM_POLICY_SJF || kind == SSIM_POLICY_SJF_CP; }
+static bool wfair_kind(int32_t kind) { return kind >= SSIM_POLICY_WFAIR_BASE && kind <= SSIM_POLICY_WFAIR_LAST; }
 static RolloutFn pick_prio(const Params& p) {
   return unit_of(p, prio_unit) == kPrioLds ? rollout_prio_lds() : rollout_prio_hbm();
 }
+static RolloutFn pick_wfair(const Params& p) {
+  return unit_of(p, wfair_unit) == kWfairLds ? rollout_wfair_lds() : rollout_wfair_hbm();
+}
 static bool known_kind(int32_t kind) {
-  return kind == SSIM_POLICY_FAIR || kind == SSIM_POLICY_FIFO || kind == SSIM_POLICY_RANDOM || prio_kind(kind);
+  return kind == SSIM_POLICY_FAIR || kind == SSIM_POLICY_FIFO || kind == SSIM_POLICY_RANDOM || prio_kind(kind) ||
+         wfair_kind(kind);
 }
 
 // ------------------------------------------------------------------------------------------ C ABI
@@ -222,6 +241,14 @@ static int set_err(int code, const char* fmt, ...) {
   vsnprintf(g_err, sizeof(g_err), fmt, ap);
   va_end(ap);
   return code;
+}
+
+// (the weighted-fair kinds encode 2 * alpha + 4 in 0..8 above their base: a kind just past them gets the range)
+static int unknown_kind(const char* who, int32_t kind) {
+  if (kind > SSIM_POLICY_WFAIR_LAST && kind < SSIM_POLICY_WFAIR_BASE + 0x100)
+    return set_err(SSIM_E_ARG, "%s: unknown policy %d (weighted fair is 0x%x..0x%x: alpha in [-2, 2])", who, kind,
+                   SSIM_POLICY_WFAIR_BASE, SSIM_POLICY_WFAIR_LAST);
+  return set_err(SSIM_E_ARG, "%s: unknown policy %d", who, kind);
 }
 
 static int hip_check(hipError_t e, const char* what) {
@@ -383,7 +410,7 @@ extern "C" int ssim_step(ssim_handle* h, const int32_t* stage_idx, const int32_t
 extern "C" int ssim_policy(ssim_handle* h, int32_t kind, uint64_t seed, uint64_t counter, int32_t* stage_idx,
                            int32_t* num_exec, void* stream) {
   if (h == nullptr || stage_idx == nullptr || num_exec == nullptr) return set_err(SSIM_E_ARG, "ssim_policy: null");
-  if (!known_kind(kind)) return set_err(SSIM_E_ARG, "ssim_policy: unknown policy %d", kind);
+  if (!known_kind(kind)) return unknown_kind("ssim_policy", kind);
   if (kind == SSIM_POLICY_SJF_CP && h->params.C.max_stages > kPrioMaxStages)
     return set_err(SSIM_E_ARG, "ssim_policy: SSIM_POLICY_SJF_CP supports at most %d stages per job (max_stages %d)",
                    kPrioMaxStages, h->params.C.max_stages);
@@ -408,7 +435,7 @@ static int rollout_launch(ssim_handle* h, int32_t kind, uint64_t seed, int32_t n
                           int32_t flags, const double* time_limits, int32_t* action_log, void* stream,
                           const int32_t* env_steps = nullptr, uint64_t* prof_out = nullptr) {
   if (h == nullptr || num_steps < 0 || budget < 0) return set_err(SSIM_E_ARG, "ssim_rollout: bad argument");
-  if (!known_kind(kind)) return set_err(SSIM_E_ARG, "ssim_rollout: unknown policy %d", kind);
+  if (!known_kind(kind)) return unknown_kind("ssim_rollout", kind);
   if (kind == SSIM_POLICY_SJF_CP && h->params.C.max_stages > kPrioMaxStages)
     return set_err(SSIM_E_ARG, "ssim_rollout: SSIM_POLICY_SJF_CP supports at most %d stages per job (max_stages %d)",
                    kPrioMaxStages, h->params.C.max_stages);
@@ -420,8 +447,9 @@ static int rollout_launch(ssim_handle* h, int32_t kind, uint64_t seed, int32_t n
   if (rc0 != SSIM_OK) return rc0;
   const ssim_layout& L = h->params.L;
   const KernelSet& ks = pick_kernels(h->params);
-  const RolloutFn fn = prio_kind(kind) ? pick_prio(h->params)  // (one symbol: warm-up launches included)
-                                       : (flags & SSIM_ROLLOUT_WARMUP) ? ks.rollout_warmup : ks.rollout;
+  const RolloutFn fn = prio_kind(kind)    ? pick_prio(h->params)  // (one symbol: warm-up launches included)
+                       : wfair_kind(kind) ? pick_wfair(h->params)  // (likewise)
+                       : (flags & SSIM_ROLLOUT_WARMUP) ? ks.rollout_warmup : ks.rollout;
   const int64_t lds = h->params.O.lds_bytes;
   const int rc = lds_opt_in((const void*)fn, lds);
   if (rc != SSIM_OK) return rc;
@@ -524,6 +552,7 @@ static const char* debug_variant(const ssim_handle* h, int32_t variant, SetTrace
       return decima_unit_name(du);
     case SSIM_DEBUG_DECIMA_GREEDY: return decima_unit_name(du, true);
     case SSIM_DEBUG_PRIO: return prio_unit_name(unit_of(p, prio_unit));
+    case SSIM_DEBUG_WFAIR: return wfair_unit_name(unit_of(p, wfair_unit));
     case SSIM_DEBUG_KAT_BAD:
       if (!shape_n100(p.L) || p.O.lds_resident) return nullptr;
       *fn = set_trace_kat_bad();
@@ -558,6 +587,15 @@ extern "C" int ssim_debug_set_trace_ex(ssim_handle* h, const int32_t* ops, int32
 extern "C" int ssim_debug_set_trace(ssim_handle* h, const int32_t* ops, int32_t n_ops, int32_t width, int32_t* orders,
                                     void* stream) {
   return ssim_debug_set_trace_ex(h, ops, n_ops, width, orders, SSIM_DEBUG_ENGINE, stream);
+}
+
+extern "C" int ssim_debug_wfair(const double* W, int32_t n, int32_t alpha2, int32_t num_executors, double* p, double* P,
+                                int32_t* cap, void* stream) {
+  if (W == nullptr || p == nullptr || P == nullptr || cap == nullptr || n < 1 || n > 4096 || alpha2 < -4 ||
+      alpha2 > 4 || num_executors < 1)
+    return set_err(SSIM_E_ARG, "ssim_debug_wfair: bad argument");
+  hipLaunchKernelGGL(k_debug_wfair, dim3(1), dim3(64), 0, (hipStream_t)stream, W, n, alpha2, num_executors, p, P, cap);
+  return hip_check(hipGetLastError(), "k_debug_wfair launch");
 }
 
 extern "C" int ssim_decima_features(ssim_handle* h, float num_tasks_scale, float work_scale, float* node_feats,

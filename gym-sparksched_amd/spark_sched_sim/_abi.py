@@ -16,6 +16,7 @@ SSIM_ROLLOUT_GREEDY = 0x10  # ssim_decima_rollout only: arg-max actions instead 
 SSIM_DEBUG_ENGINE, SSIM_DEBUG_DECIMA, SSIM_DEBUG_KAT_BAD = 0, 1, 2  # ssim_debug_set_trace_ex variants
 SSIM_DEBUG_PRIO = 3  # ssim_debug_kernel_name only: the SJF / SJF-CP rollout unit of a handle
 SSIM_DEBUG_DECIMA_GREEDY = 4  # ssim_debug_kernel_name only: the unit of a SSIM_ROLLOUT_GREEDY launch
+SSIM_DEBUG_WFAIR = 5  # ssim_debug_kernel_name only: the weighted-fair rollout unit of a handle
 SSIM_ACT_LEAKY_RELU, SSIM_ACT_TANH = 0, 1  # ssim_mlp3_* activations
 SSIM_ERR_SPACE = 0x1
 SSIM_ERR_KEY = 0x2
@@ -35,6 +36,34 @@ SSIM_POLICY_SJF_CP = 5  # shortest job first, its schedulable stage with the lon
 # scheduler name -> device policy kind (examples.py --sched, evaluate.evaluate_policy)
 POLICY_KINDS = {"fair": SSIM_POLICY_FAIR, "fifo": SSIM_POLICY_FIFO, "random": SSIM_POLICY_RANDOM,
                 "sjf": SSIM_POLICY_SJF, "sjf-cp": SSIM_POLICY_SJF_CP}
+# Weighted fair (executors in proportion to work^alpha): the exponent is part of the kind, SSIM_POLICY_WFAIR_BASE +
+# (2 alpha + 4) for the half-integers alpha in [-2, 2]. Not in POLICY_KINDS: a name alone does not give the kind.
+SSIM_POLICY_WFAIR_BASE = 0x100
+WFAIR_ALPHAS = tuple(a2 / 2 for a2 in range(-4, 5))
+
+
+def wfair_kind(alpha) -> int:
+    """The device policy kind of weighted fair with exponent `alpha` (a half-integer in [-2, 2])."""
+    try:
+        a2 = 2.0 * float(alpha)
+    except (TypeError, ValueError):
+        raise ValueError(f"weighted fair: alpha must be a number, not {alpha!r}") from None
+    if not -4 <= a2 <= 4 or a2 != int(a2):  # (a nan fails the range test)
+        raise ValueError(f"weighted fair: alpha must be a half-integer in [-2, 2] (one of {list(WFAIR_ALPHAS)}), "
+                         f"not {alpha!r}")
+    return SSIM_POLICY_WFAIR_BASE + int(a2) + 4
+
+
+def is_wfair_kind(kind) -> bool:
+    return SSIM_POLICY_WFAIR_BASE <= int(kind) <= SSIM_POLICY_WFAIR_BASE + 8
+
+
+def wfair_alpha(kind) -> float:
+    """The exponent of a weighted-fair policy kind."""
+    if not is_wfair_kind(kind):
+        raise ValueError(f"policy kind {kind} is not a weighted-fair kind "
+                         f"({SSIM_POLICY_WFAIR_BASE:#x}..{SSIM_POLICY_WFAIR_BASE + 8:#x})")
+    return (int(kind) - SSIM_POLICY_WFAIR_BASE - 4) / 2
 
 # indices into the per-env int32 counts block
 OC_NUM_NODES, OC_NUM_EDGES, OC_NUM_JOBS, OC_COMMITTABLE, OC_SOURCE_JOB_IDX, OC_NUM_SCHEDULABLE = range(6)

@@ -4,7 +4,8 @@
 one kernel, `DeviceEngine.rollout`) until every episode has terminated, and returns each env's average job duration
 in seconds computed like `metrics.avg_job_duration` — the number `examples.py` prints for one env driven from the
 host, here for thousands of envs with no host round trip per decision. It takes any policy kind of
-`_abi.POLICY_KINDS` (fair, fifo, random, sjf, sjf-cp), by name or by its SSIM_POLICY_* value, or "decima" with
+`_abi.POLICY_KINDS` (fair, fifo, random, sjf, sjf-cp), by name or by its SSIM_POLICY_* value, "wfair" with `alpha=` a
+half-integer in [-2, 2] (weighted fair; `tune_weighted_fair` sweeps the exponent), or "decima" with
 `policy=` a `DecimaScheduler` or a checkpoint path (`DecimaScheduler.save`): the persistent Decima rollout, greedy
 (arg-max actions, `_abi.SSIM_ROLLOUT_GREEDY`) or sampled, on the same seeds as the heuristics.
 
@@ -67,8 +68,11 @@ def job_table_stats(engine) -> np.ndarray:
 
 def evaluate_policy(env_cfg: dict, kind, seeds, device=None, dataset=None, engine_factory=None,
                     max_launches: int = 64, steps_per_launch: int = 256, policy_seed: int = 0, policy=None,
-                    greedy: bool = True, action_log: list | None = None) -> dict:
+                    greedy: bool = True, action_log: list | None = None, alpha=None) -> dict:
     """Runs one episode per seed under device policy `kind` to termination.
+
+    kind "wfair": weighted fair with exponent `alpha` (a half-integer in [-2, 2], default -1; `_abi.wfair_kind`), or
+    one of the weighted-fair kinds by value. `alpha=` with any other kind is a ValueError.
 
     kind "decima": `policy` is a `DecimaScheduler` or the path of a checkpoint (`DecimaScheduler.save`); every launch
     is a persistent Decima rollout of up to `steps_per_launch` decisions per env, with the arg-max action (`greedy`,
@@ -93,7 +97,14 @@ def evaluate_policy(env_cfg: dict, kind, seeds, device=None, dataset=None, engin
     else:
         if policy is not None:
             raise ValueError("evaluate_policy: policy= goes with kind 'decima' only")
-        kind = policy_kind(kind)
+        if isinstance(kind, str) and kind == "wfair":
+            kind = _abi.wfair_kind(-1.0 if alpha is None else alpha)
+        elif alpha is not None:
+            raise ValueError(f"evaluate_policy: alpha= goes with kind 'wfair' only, not {kind!r}")
+        elif not isinstance(kind, str) and _abi.is_wfair_kind(kind):
+            kind = int(kind)
+        else:
+            kind = policy_kind(kind)
     seeds = [int(s) for s in seeds]
     dataset = resolve_dataset(env_cfg, dataset)
     if engine_factory is None:
@@ -154,3 +165,20 @@ def evaluate_policy(env_cfg: dict, kind, seeds, device=None, dataset=None, engin
                 "launches": launches}
     finally:
         engine.close()
+
+
+def tune_weighted_fair(env_cfg: dict, seeds, alphas=None, **kw) -> dict:
+    """The tuned weighted-fair baseline: one `evaluate_policy(env_cfg, "wfair", seeds, alpha=a, **kw)` per exponent of
+    `alphas` (default: the nine half-integers of [-2, 2]) and the exponent with the smallest mean average job duration
+    over the seeds; ties go to the smaller |alpha|, then to the smaller alpha.
+
+    Returns {"alpha": best, "mean_avg_job_duration": {alpha: mean over seeds, seconds}, "per_seed": {alpha: float64
+    [len(seeds)]}}."""
+    seeds = [int(s) for s in seeds]
+    alphas = list(_abi.WFAIR_ALPHAS) if alphas is None else [_abi.wfair_alpha(_abi.wfair_kind(a)) for a in alphas]
+    if not alphas:
+        raise ValueError("tune_weighted_fair: no exponent to try")
+    per_seed = {a: evaluate_policy(env_cfg, "wfair", seeds, alpha=a, **kw)["avg_job_duration"] for a in alphas}
+    mean = {a: float(np.mean(d)) for a, d in per_seed.items()}
+    best = min(mean, key=lambda a: (mean[a], abs(a), a))
+    return {"alpha": best, "mean_avg_job_duration": mean, "per_seed": per_seed}

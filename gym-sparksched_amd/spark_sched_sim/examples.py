@@ -6,6 +6,7 @@ average job duration in seconds (`metrics.avg_job_duration(env) * 1e-3`).
 
     python -m spark_sched_sim.examples --sched fair      # examples.py --sched fair (BASELINE configs[0])
     python -m spark_sched_sim.examples --sched sjf-cp    # shortest job first, critical-path stage choice
+    python -m spark_sched_sim.examples --sched wfair --alpha -1   # weighted fair: executors in proportion to work^alpha
     python -m spark_sched_sim.examples --sched decima --model decima.pt   # a DecimaScheduler.save checkpoint, greedy
                                                                           # (--sample: draw the actions instead)
 """
@@ -66,7 +67,9 @@ class DecimaHostScheduler:
 
 def main(argv=None) -> None:
     parser = ArgumentParser(description=__doc__, formatter_class=ArgumentDefaultsHelpFormatter)
-    parser.add_argument("--sched", choices=list(POLICY_KINDS) + ["decima"], required=True)
+    parser.add_argument("--sched", choices=list(POLICY_KINDS) + ["wfair", "decima"], required=True)
+    parser.add_argument("--alpha", type=float, default=None,
+                        help="--sched wfair: the work exponent, a half-integer in [-2, 2] (default -1)")
     parser.add_argument("--seed", type=int, default=1234)
     parser.add_argument("--model", default=None, help="--sched decima: a DecimaScheduler.save checkpoint")
     parser.add_argument("--sample", action="store_true", help="--sched decima: draw the actions (default: arg-max)")
@@ -83,7 +86,10 @@ def main(argv=None) -> None:
                            f"{ENV_CFG['num_executors']}\n")
         scheduler = DecimaHostScheduler(model, sample=args.sample, seed=42)
     else:
-        scheduler = host_scheduler(args.sched, ENV_CFG["num_executors"], seed=42)
+        try:
+            scheduler = host_scheduler(args.sched, ENV_CFG["num_executors"], seed=42, alpha=args.alpha)
+        except ValueError as e:  # (--alpha off the grid, or given with another scheduler)
+            parser.exit(2, f"{e}\n")
     print(f"Example: {scheduler.name} Scheduler")
     print("Env settings:")
     pprint(ENV_CFG)

@@ -47,6 +47,7 @@ _PROTOTYPES = [
     ("ssim_debug_set_trace", ct.c_int, [_vp, _vp, _i32, _i32, _vp, _vp]),
     ("ssim_debug_set_trace_ex", ct.c_int, [_vp, _vp, _i32, _i32, _vp, _i32, _vp]),
     ("ssim_debug_kernel_name", ct.c_char_p, [_vp, _i32]),
+    ("ssim_debug_wfair", ct.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     ("ssim_linear_fwd", ct.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp]),
     ("ssim_linear_wgrad_parts", _i32, [_i64]),
     ("ssim_linear_wgrad", ct.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _i32, _vp]),

@@ -115,6 +115,94 @@ class RandomScheduler(Scheduler):
         return {"stage_idx": k, "num_exec": num_exec}, {}
 
 
+class WeightedFairScheduler(Scheduler):
+    """Weighted fair, WFair(alpha): the fair scheduler with the executors shared in proportion to work^alpha; the
+    specification the device kinds `SSIM_POLICY_WFAIR_BASE + (2 alpha + 4)` (csrc/policy.h wfair_act) follow action
+    for action. alpha is a half-integer in [-2, 2] (alpha2 = 2 alpha), so that every step is one correctly rounded
+    float64 operation (multiply, divide, square root, add) and numpy, the host build and the device agree bit for bit.
+
+    W(k): `ShortestJobFirstScheduler.job_work`. p(k) = h(W(k), alpha2) for W(k) > 0, with h(w, a) for a = 0..4 being
+    1, sqrt(w), w, w * sqrt(w), w * w and 1 / h(w, -a) for a < 0; for W(k) == 0, p(k) is 1 if alpha2 == 0, else 0.
+    P = the sum of p in blocks of 64 consecutive jobs (zero-padded), each block folded by halves (x[:32] + x[32:], then
+    16, 8, 4, 2, 1), the block sums added left to right from 0.0. cap(k) = min(N, ceil((N * p(k)) / P)).
+    The action is `RoundRobinScheduler`'s with that cap: the source job with every committable executor if it has a
+    schedulable stage; else the first job k != src in arrival order with supply(k) < cap(k) and a schedulable stage,
+    with min(committable, cap(k) - supply(k)) executors; else (and whenever P == 0) stage_idx -1. alpha = 0 is the
+    fair scheduler. A pure function of the observation."""
+
+    def __init__(self, num_executors: int, alpha: float = -1.0, **kwargs):
+        from .._abi import wfair_alpha, wfair_kind
+
+        self.kind = wfair_kind(alpha)  # (ValueError off the grid)
+        self.alpha = wfair_alpha(self.kind)
+        self.alpha2 = int(2 * self.alpha)
+        self.name = f"WFair({self.alpha:g})"
+        self.num_executors = num_executors
+        self.env_wrapper_cls = None
+
+    @staticmethod
+    def weight(w, alpha2: int) -> np.float64:
+        """p = w^(alpha2 / 2) by the rule's operations."""
+        w = np.float64(w)
+        if not w > 0.0:
+            return np.float64(1.0 if alpha2 == 0 else 0.0)
+        a = abs(alpha2)
+        h = (np.float64(1.0), np.sqrt(w), w, w * np.sqrt(w), w * w)[a]
+        return np.float64(1.0) / h if alpha2 < 0 else h
+
+    @staticmethod
+    def total(p) -> np.float64:
+        """P: the fold-halves sum of each block of 64 weights, the block sums added left to right."""
+        p = np.asarray(p, dtype=np.float64)
+        total = np.float64(0.0)
+        for k0 in range(0, len(p), 64):
+            x = np.zeros(64, dtype=np.float64)
+            x[:len(p[k0:k0 + 64])] = p[k0:k0 + 64]
+            half = 32
+            while half:
+                x = x[:half] + x[half:2 * half]
+                half //= 2
+            total = total + x[0]
+        return total
+
+    def cap(self, p, total) -> int:
+        """min(N, ceil((N * p) / P)) for P > 0."""
+        c = np.ceil((np.float64(self.num_executors) * np.float64(p)) / np.float64(total))
+        return int(c) if c < self.num_executors else self.num_executors
+
+    def weights(self, obs: dict) -> list:
+        w = ShortestJobFirstScheduler.row_work(obs)
+        return [self.weight(ShortestJobFirstScheduler.job_work(obs, w, k), self.alpha2)
+                for k in range(len(obs["exec_supplies"]))]
+
+    def other_jobs(self, obs: dict, p, total) -> dict:
+        """The action when the source job is not served, from the weights `p` and their sum `total` (after
+        preprocess_obs): the first job other than the source under its cap with a schedulable stage."""
+        supplies = obs["exec_supplies"]
+        committable = obs["num_committable_execs"]
+        if total > 0.0:
+            for j in range(len(supplies)):
+                if j == obs["source_job_idx"]:
+                    continue
+                cap = self.cap(p[j], total)
+                if supplies[j] >= cap:
+                    continue
+                k = find_stage(obs, j)
+                if k != -1:
+                    return {"stage_idx": k, "num_exec": min(committable, cap - supplies[j])}
+        return {"stage_idx": -1, "num_exec": committable}
+
+    def schedule(self, obs: dict) -> tuple[dict, dict]:
+        preprocess_obs(obs)
+        src = obs["source_job_idx"]
+        if src < len(obs["exec_supplies"]):
+            k = find_stage(obs, src)
+            if k != -1:
+                return {"stage_idx": k, "num_exec": obs["num_committable_execs"]}, {}
+        p = self.weights(obs)
+        return self.other_jobs(obs, p, self.total(p)), {}
+
+
 class ShortestJobFirstScheduler(Scheduler):
     """Shortest job first, optionally with critical-path stage choice (SJF / SJF-CP); the specification the device
     kinds `SSIM_POLICY_SJF` / `SSIM_POLICY_SJF_CP` (csrc/policy.h) follow action for action.

@@ -101,8 +101,8 @@ class SparkSchedSimVecEnv:
 
     def policy(self, kind: int = _abi.SSIM_POLICY_FAIR, seed: int = 0, counter: int = 0):
         """On-device action driver: `kind` is one of _abi.SSIM_POLICY_FAIR / _FIFO / _RANDOM / _SJF / _SJF_CP
-        (_abi.POLICY_KINDS by name; seed / counter feed the random kind only, SJF-CP needs max_stages <= 64);
-        returns (stage_idx, num_exec) tensors."""
+        (_abi.POLICY_KINDS by name; seed / counter feed the random kind only, SJF-CP needs max_stages <= 64) or a
+        weighted-fair kind, _abi.wfair_kind(alpha); returns (stage_idx, num_exec) tensors."""
         return self.engine.policy(kind, seed, counter)
 
     def rollout(self, kind: int, seed: int, num_steps: int, action_log=None):

@@ -56,6 +56,19 @@ extern "C" {
  * run-time-shape kernels of either residency (ssim_debug_kernel_name(h, SSIM_DEBUG_PRIO)). */
 #define SSIM_POLICY_SJF 4
 #define SSIM_POLICY_SJF_CP 5
+/* Weighted fair: executors shared in proportion to work^alpha, alpha a half-integer in [-2, 2]. The exponent is part of
+ * the kind: kind = SSIM_POLICY_WFAIR_BASE + (alpha2 + 4) with alpha2 = 2 * alpha in -4..4, so 0x100..0x108 (0x109 and
+ * above: SSIM_E_ARG). W(k) is SJF's job work. The weight p(k) is, for alpha2 = 0..4, 1, sqrt(W), W, W * sqrt(W), W * W
+ * and its reciprocal for a negative alpha2; a job with W = 0 weighs 1 when alpha2 = 0, else 0. P is the sum of p in
+ * blocks of 64 jobs (zero-padded), each block folded by halves (x[:32] + x[32:], 16, 8, 4, 2, 1), the block sums added
+ * left to right. cap(k) = min(N, ceil((N * p(k)) / P)). The action is RoundRobinScheduler's with that cap: the source
+ * job with all committable executors if it has a schedulable stage, else the first job in arrival order under its cap
+ * with min(committable, cap - supply); stage_idx -1 if there is none or P = 0. Every operation is one correctly rounded
+ * float64 operation. alpha2 = 0 is SSIM_POLICY_FAIR action for action. seed / counter are ignored; the fused rollouts
+ * run these kinds on run-time-shape kernels of their own, one per residency
+ * (ssim_debug_kernel_name(h, SSIM_DEBUG_WFAIR)). */
+#define SSIM_POLICY_WFAIR_BASE 0x100
+#define SSIM_POLICY_WFAIR_LAST 0x108
 
 /* Env configuration (spark_sched_sim.py:37-52, tpch.py:19-49). */
 typedef struct ssim_config {
@@ -409,11 +422,17 @@ int ssim_debug_set_trace(ssim_handle* h, const int32_t* ops, int32_t n_ops, int3
 #define SSIM_DEBUG_KAT_BAD 2
 #define SSIM_DEBUG_PRIO 3 /* ssim_debug_kernel_name only: the unit an SJF / SJF-CP rollout on this handle launches */
 #define SSIM_DEBUG_DECIMA_GREEDY 4 /* ssim_debug_kernel_name only: the unit of a SSIM_ROLLOUT_GREEDY launch ("drg_*") */
+#define SSIM_DEBUG_WFAIR 5 /* ssim_debug_kernel_name only: the unit a weighted-fair rollout on this handle launches */
 int ssim_debug_set_trace_ex(ssim_handle* h, const int32_t* ops, int32_t n_ops, int32_t width, int32_t* orders,
                             int32_t variant, void* stream);
 /* Name of the kernel translation unit a variant selects for this handle ("hbm_n100", "bench900", "dr_hbm50", ...; ""
  * when the variant does not apply). */
 const char* ssim_debug_kernel_name(const ssim_handle* h, int32_t variant);
+/* Known-answer test of the weighted-fair arithmetic (SSIM_POLICY_WFAIR_BASE), one wave, through the device functions the
+ * policy uses: W device float64 [n] job works (1 <= n <= 4096), alpha2 in -4..4; writes p [n] (the weights), P [1] (their
+ * sum in the rule's order) and cap [n] (all 0 when P = 0). */
+int ssim_debug_wfair(const double* W, int32_t n, int32_t alpha2, int32_t num_executors, double* p, double* P,
+                     int32_t* cap, void* stream);
 
 /* The PPO learner's small dense layers (widths <= 64: the Decima MLPs) on the device, replacing the nn.Linear GEMMs
  * of trainers/ppo.py's evaluate_actions passes (reference: schedulers/decima/utils.py:51-70 make_mlp, trained by
