@@ -20,6 +20,7 @@
 #include "decima.h"
 #include "decima_policy.h"
 #include "decima_rollout.h"
+#include "teacher_rollout.h"
 #include "units.h"
 
 // ------------------------------------------------------------------------------------------ kernels
@@ -553,6 +554,7 @@ static const char* debug_variant(const ssim_handle* h, int32_t variant, SetTrace
     case SSIM_DEBUG_DECIMA_GREEDY: return decima_unit_name(du, true);
     case SSIM_DEBUG_PRIO: return prio_unit_name(unit_of(p, prio_unit));
     case SSIM_DEBUG_WFAIR: return wfair_unit_name(unit_of(p, wfair_unit));
+    case SSIM_DEBUG_TEACHER: return teacher_unit_name(unit_of(p, teacher_unit));
     case SSIM_DEBUG_KAT_BAD:
       if (!shape_n100(p.L) || p.O.lds_resident) return nullptr;
       *fn = set_trace_kat_bad();
@@ -885,6 +887,75 @@ extern "C" int ssim_decima_rollout_timed(ssim_handle* h, const float* params, in
                      dparams(h), h->state, h->obs, a, t, max_steps, flags, h->reset, action_log, h->prof_next);
   h->prof_next = nullptr;
   return hip_check(hipGetLastError(), "k_decima_rollout_timed launch");
+}
+
+// The teacher rollout's LDS plan (teacher_rollout.h): the Decima rollout's plan of a one-wave unit (decima_lds_plan: the
+// same engine configuration, so what the plan overlays or follows is the same, and the same share of the CU), of which
+// the teacher uses the features' scratch only. A decision takes the LDS under the rule of decima_rollout.h
+// DecimaPolicy::act (at most `cap` nodes and kDpLdsDags DAGs), so a teacher collection runs the features where a Decima
+// collection of the same observations runs them, and both placements occur at small shapes.
+static DecimaLdsPlan teacher_lds_plan(const Params& P) { return decima_lds_plan(P, 1); }
+static TeacherRolloutFn pick_teacher(const Params& p) {
+  return unit_of(p, teacher_unit) == kTrLds ? teacher_rollout_lds() : teacher_rollout_hbm();
+}
+
+extern "C" int ssim_debug_teacher_plan(const ssim_handle* h, int32_t* cap, int32_t* dags) {
+  if (h == nullptr || cap == nullptr || dags == nullptr)
+    return set_err(SSIM_E_ARG, "ssim_debug_teacher_plan: null argument");
+  *cap = teacher_lds_plan(h->params).cap;
+  *dags = kDpLdsDags;
+  return SSIM_OK;
+}
+
+extern "C" int ssim_teacher_rollout(ssim_handle* h, int32_t kind, uint64_t seed, float num_tasks_scale,
+                                    float work_scale, int32_t max_steps, int32_t flags, void* workspace,
+                                    int64_t workspace_bytes, const ssim_decima_samples* samples, int32_t* action_log,
+                                    void* stream) {
+  if (h == nullptr || workspace == nullptr || max_steps < 0)
+    return set_err(SSIM_E_ARG, "ssim_teacher_rollout: bad argument");
+  if (!known_kind(kind)) return unknown_kind("ssim_rollout", kind);
+  if (kind == SSIM_POLICY_SJF_CP && h->params.C.max_stages > kPrioMaxStages)
+    return set_err(SSIM_E_ARG, "ssim_teacher_rollout: SSIM_POLICY_SJF_CP supports at most %d stages per job "
+                   "(max_stages %d)", kPrioMaxStages, h->params.C.max_stages);
+  if (flags != 0)
+    return set_err(SSIM_E_ARG, "ssim_teacher_rollout: collection mode only, flags must be 0 (no SSIM_ROLLOUT_AUTORESET / "
+                   "PREEMPT / WARMUP / GREEDY; flags 0x%x)", flags);
+  if (h->params.C.max_stages > kDecimaMaxDepth)
+    return set_err(SSIM_E_ARG, "ssim_teacher_rollout: max_stages %d > %d (edge-mask word)", h->params.C.max_stages,
+                   kDecimaMaxDepth);
+  if (samples == nullptr) return set_err(SSIM_E_ARG, "ssim_teacher_rollout: needs a sample arena");
+  const ssim_decima_samples& sm = *samples;
+  if (sm.cursor == nullptr || sm.rec == nullptr || sm.nodes == nullptr || sm.edges == nullptr || sm.dags == nullptr ||
+      sm.cap_samples <= 0 || sm.cap_nodes < 0 || sm.cap_edges < 0 || sm.cap_dags < 0)
+    return set_err(SSIM_E_ARG, "ssim_teacher_rollout: incomplete sample arena");
+  const ssim_layout& L = h->params.L;
+  const DecimaWork wl = decima_work(L);
+  if (workspace_bytes < wl.total)
+    return set_err(SSIM_E_ARG, "ssim_teacher_rollout: workspace of %lld B, needs %lld (ssim_decima_workspace_bytes)",
+                   (long long)workspace_bytes, (long long)wl.total);
+  uint8_t* const work = static_cast<uint8_t*>(workspace);
+  const DecimaLdsPlan pl = teacher_lds_plan(h->params);
+  TeacherArgs a{};
+  a.work = work + wl.feat_scratch;
+  a.stride = wl.stride;
+  a.feats = reinterpret_cast<float*>(work + wl.feats);
+  a.ccap = reinterpret_cast<int32_t*>(work + wl.ccap);
+  a.emask = reinterpret_cast<uint32_t*>(work + wl.emask);
+  a.depth = reinterpret_cast<int32_t*>(work + wl.depth);
+  a.num_tasks_scale = num_tasks_scale;
+  a.work_scale = work_scale;
+  a.kind = kind;
+  a.seed = seed;
+  a.plan_cap = pl.cap;
+  a.plan_off = pl.off;
+  a.plan_dags = kDpLdsDags;
+  a.smp = sm;
+  const TeacherRolloutFn fn = pick_teacher(h->params);
+  const int rc = lds_opt_in((const void*)fn, pl.lds);
+  if (rc != SSIM_OK) return rc;
+  hipLaunchKernelGGL(fn, dim3(L.num_envs), dim3(64), (size_t)pl.lds, (hipStream_t)stream, dparams(h), h->state, h->obs,
+                     a, max_steps, h->reset, action_log);
+  return hip_check(hipGetLastError(), "k_teacher_rollout launch");
 }
 
 extern "C" const char* ssim_last_error(void) { return g_err; }

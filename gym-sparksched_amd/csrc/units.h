@@ -10,6 +10,7 @@ enum EngineUnit : int { kEngBench900, kEngBench, kEngLds, kEngHbm, kEngHbmN100, 
 enum DecimaUnit : int { kDrHbm, kDrHbm50, kDrLds, kDrLds50, kNumDecimaUnits };  // k_dr_* with their k_drt_* / k_drg_*
 enum PrioUnit : int { kPrioLds, kPrioHbm, kNumPrioUnits };
 enum WfairUnit : int { kWfairLds, kWfairHbm, kNumWfairUnits };
+enum TeacherUnit : int { kTrLds, kTrHbm, kNumTeacherUnits };  // k_tr_*: the teacher rollout (teacher_rollout.h)
 
 // The shapes with kernels of their own: BASELINE configs[1] (10 executors, 50 jobs), decima_tpch.yaml (50, 200), the
 // configs[3] shard (100, 200).
@@ -36,6 +37,8 @@ inline DecimaUnit decima_unit(const ssim_layout& L, bool lds_resident, bool gene
 inline PrioUnit prio_unit(const ssim_layout&, bool lds_resident, bool) { return lds_resident ? kPrioLds : kPrioHbm; }
 // The weighted-fair kinds likewise, in units of their own (k_wfair_*.hip).
 inline WfairUnit wfair_unit(const ssim_layout&, bool lds_resident, bool) { return lds_resident ? kWfairLds : kWfairHbm; }
+// The teacher rollout (every policy kind in one kernel) likewise (k_tr_*.hip).
+inline TeacherUnit teacher_unit(const ssim_layout&, bool lds_resident, bool) { return lds_resident ? kTrLds : kTrHbm; }
 
 // Waves per env's workgroup of a Decima unit: dr_lds50 has the exec-score helper waves (decima_policy.h kDpHelpWaves,
 // which sparksched.hip asserts equal to this).
@@ -54,6 +57,7 @@ inline const char* decima_unit_name(DecimaUnit u, bool greedy = false) {
 }
 inline const char* prio_unit_name(PrioUnit u) { return u == kPrioLds ? "prio_lds" : "prio_hbm"; }
 inline const char* wfair_unit_name(WfairUnit u) { return u == kWfairLds ? "wfair_lds" : "wfair_hbm"; }
+inline const char* teacher_unit_name(TeacherUnit u) { return u == kTrLds ? "tr_lds" : "tr_hbm"; }
 constexpr const char* kKatBadName = "kat_bad_page";  // the test-only known-bad page assembly (k_hbm_n100.hip)
 
 }  // namespace ssim

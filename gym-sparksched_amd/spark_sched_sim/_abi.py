@@ -17,6 +17,7 @@ SSIM_DEBUG_ENGINE, SSIM_DEBUG_DECIMA, SSIM_DEBUG_KAT_BAD = 0, 1, 2  # ssim_debug
 SSIM_DEBUG_PRIO = 3  # ssim_debug_kernel_name only: the SJF / SJF-CP rollout unit of a handle
 SSIM_DEBUG_DECIMA_GREEDY = 4  # ssim_debug_kernel_name only: the unit of a SSIM_ROLLOUT_GREEDY launch
 SSIM_DEBUG_WFAIR = 5  # ssim_debug_kernel_name only: the weighted-fair rollout unit of a handle
+SSIM_DEBUG_TEACHER = 6  # ssim_debug_kernel_name only: the teacher rollout unit of a handle (tr_lds / tr_hbm)
 SSIM_ACT_LEAKY_RELU, SSIM_ACT_TANH = 0, 1  # ssim_mlp3_* activations
 SSIM_ERR_SPACE = 0x1
 SSIM_ERR_KEY = 0x2

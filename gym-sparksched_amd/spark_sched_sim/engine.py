@@ -420,6 +420,21 @@ class DeviceEngine:
         self._native.check(self._native.lib().ssim_decima_rollout(*args, _ptr(action_log), self._stream()),
                            "ssim_decima_rollout")
 
+    def teacher_rollout(self, kind: int, seed: int, steps: int, samples, num_tasks_scale: float = 200.0,
+                        work_scale: float = 1e5, action_log=None, flags: int = 0):
+        """ssim_teacher_rollout: the device heuristic `kind` (any of _abi.POLICY_KINDS or _abi.wfair_kind(alpha)) drives
+        every env until its episode ends, in ONE launch, and leaves every decision in `samples` (a DecimaSampleArena) as
+        the persistent Decima rollout would: the Decima observation rows plus the heuristic's action in Decima's action
+        space (no-op decisions recorded with stage_idx = job_idx = -1). `steps`: at most that many decisions per env in
+        this launch. `flags` exists to be refused (collection mode only)."""
+        ws = self.decima_workspace()
+        st = samples.struct() if samples is not None else None
+        self._keep_tr = (st, action_log)
+        self._native.check(self._native.lib().ssim_teacher_rollout(
+            self.handle, int(kind), int(seed) & (2**64 - 1), float(num_tasks_scale), float(work_scale), int(steps),
+            int(flags), ws.data_ptr(), ws.numel(), None if st is None else ct.byref(st), _ptr(action_log),
+            self._stream()), "ssim_teacher_rollout")
+
     def decima_rollout_timed(self, params, seed: int, counter: int, max_steps: int, samples, timed,
                              flags: int = 0, total_decisions: int = 0, time_limits=None, action_log=None,
                              num_tasks_scale: float = 200.0, work_scale: float = 1e5, tensors=()):

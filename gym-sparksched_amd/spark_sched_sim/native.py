@@ -42,6 +42,8 @@ _PROTOTYPES = [
     ("ssim_decima_rollout_timed", ct.c_int, _DECIMA_ROLLOUT + [_vp, _vp, _vp]),
     ("ssim_decima_rollout_lds_bytes", _i64, [_vp]),
     ("ssim_debug_decima_plan", ct.c_int, [_vp, ct.POINTER(_i32), ct.POINTER(_i32)]),
+    ("ssim_teacher_rollout", ct.c_int, [_vp, _i32, _u64, _f32, _f32, _i32, _i32, _vp, _i64, _vp, _vp, _vp]),
+    ("ssim_debug_teacher_plan", ct.c_int, [_vp, ct.POINTER(_i32), ct.POINTER(_i32)]),
     ("ssim_last_error", ct.c_char_p, []),
     ("ssim_build_id", ct.c_char_p, []),
     ("ssim_debug_set_trace", ct.c_int, [_vp, _vp, _i32, _i32, _vp, _vp]),

@@ -7,4 +7,5 @@ from .ppo import DECIMA_TPCH, PPO, make_trainer  # noqa: F401
 from .returns import Baseline, ReturnsCalculator  # noqa: F401
 from .rollouts import (AsyncRolloutCollector, ArenaRolloutBuffer, DecimaSampleArena,  # noqa: F401
                        DeviceAsyncRolloutCollector, DeviceRolloutCollector, GpuRolloutBuffer, ResetSchedule,
-                       RolloutCollector)
+                       RolloutCollector, TeacherRolloutCollector)
+from .imitation import BehaviourCloning  # noqa: F401

@@ -106,10 +106,18 @@ class PPO:
             raise ValueError(f"{self.rows} rollout rows cannot be split over {self.world} ranks")
         self.row_lo, self.row_hi = split_rows(self.rows, self.world, self.rank)
         self.baseline = Baseline(self.num_sequences, self.num_rollouts)  # learner side, over all rows
-        kw = {k: v for k, v in agent_cfg.items() if k != "agent_cls"}
+        kw = {k: v for k, v in agent_cfg.items() if k not in ("agent_cls", "init_checkpoint")}
         self.scheduler = DecimaScheduler(env_cfg["num_executors"], opt_cls=train_cfg.get("opt_cls", "Adam"),
                                          opt_kwargs=train_cfg.get("opt_kwargs"),
                                          max_grad_norm=train_cfg.get("max_grad_norm"), **kw).to(self.device)
+        if agent_cfg.get("init_checkpoint"):
+            # the starting point: a DecimaScheduler.save checkpoint (e.g. a behaviour-cloned policy,
+            # trainers/imitation.py), read on every rank before the first collection and the first broadcast
+            init = DecimaScheduler.load(agent_cfg["init_checkpoint"])
+            if init.num_executors != self.scheduler.num_executors:
+                raise ValueError(f"init_checkpoint {agent_cfg['init_checkpoint']}: {init.num_executors} executors, the "
+                                 f"env has {self.scheduler.num_executors}")
+            self.scheduler.load_state_dict(init.state_dict())
         B = self.row_hi - self.row_lo
         if dataset is None:
             from ..env import resolve_dataset

@@ -619,3 +619,73 @@ class DeviceAsyncRolloutCollector(AsyncRolloutCollector):
         buf = self.arena.buffer(self.clock[:, 0].clone())  # times are elapsed times: the final one closes each row
         buf.resets = sorted(resets, key=lambda r: (r[1], r[0]))  # (env, step) in the lockstep loop's order
         return buf
+
+
+def teacher_kind(teacher, alpha=None) -> int:
+    """The device policy kind of a teacher: a name of _abi.POLICY_KINDS, "wfair" with its exponent `alpha`, or a kind."""
+    if isinstance(teacher, str):
+        if teacher == "wfair":
+            if alpha is None:
+                raise ValueError('teacher "wfair" needs alpha (a half-integer in [-2, 2])')
+            return _abi.wfair_kind(alpha)
+        if teacher not in _abi.POLICY_KINDS:
+            raise ValueError(f"unknown teacher {teacher!r} (one of {sorted(_abi.POLICY_KINDS)} or 'wfair')")
+        return _abi.POLICY_KINDS[teacher]
+    return int(teacher)
+
+
+class TeacherRolloutCollector:
+    """One collection per call with a device heuristic as the teacher (ssim_teacher_rollout, csrc/teacher_rollout.h):
+    every row is reset with its seed, its wave runs the heuristic to the end of the episode in ONE kernel launch, and
+    every decision is left in a DecimaSampleArena in the form the learner reads (the Decima observation rows and the
+    heuristic's action as stage_idx / job_idx / exec_idx). Resets, launches, grows the arena and relaunches exactly as
+    DeviceRolloutCollector.collect does. No-op decisions (stage_idx = -1) are part of the buffer: trajectories() is
+    complete, and a learner masks them out (trainers/imitation.py). `engine`: a DeviceEngine, or the test-only host
+    build with a teacher_rollout of its own."""
+
+    def __init__(self, engine, kind, alpha=None, seed: int = 0, num_tasks_scale: float = 200.0, work_scale: float = 1e5,
+                 cap_samples: int = 1024, cap_nodes: int = 1 << 16, cap_edges: int = 1 << 16, cap_dags: int = 1 << 14):
+        if not hasattr(engine, "teacher_rollout"):
+            raise ValueError("TeacherRolloutCollector needs an engine with teacher_rollout (a DeviceEngine)")
+        self.engine = engine
+        self.kind = teacher_kind(kind, alpha)
+        self.seed = int(seed)
+        self.scales = (num_tasks_scale, work_scale)
+        self.on_device = isinstance(engine.views["counts"], torch.Tensor)
+        self.arena = DecimaSampleArena(engine.num_envs, engine.device if self.on_device else "cpu", cap_samples,
+                                       cap_nodes, cap_edges, cap_dags)
+        self.calls = 0
+        self.launches = 0
+        self.growths = 0
+
+    def _host(self, name: str) -> np.ndarray:
+        v = self.engine.views[name] if self.on_device else self.engine.host_views()[name]
+        return v.cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+
+    def _check_not_frozen(self) -> None:
+        err = self._host("counts")[:, _abi.OC_ERR] & _abi.SSIM_ERR_STICKY
+        if err.any():
+            bad = np.flatnonzero(err)
+            raise RuntimeError(f"teacher rollout: envs {bad[:8].tolist()} frozen with error bits "
+                               f"{[hex(int(x)) for x in err[bad[:8]]]}")
+
+    @torch.no_grad()
+    def collect(self, seeds, time_limits=None, max_steps: int = 10**9) -> ArenaRolloutBuffer:
+        self.calls += 1
+        eng = self.engine
+        limits = None if time_limits is None else np.asarray(time_limits, dtype=np.float64)
+        eng.reset_sampled(_abi.SSIM_RESET_SEED, seeds=seeds, time_limits=limits)
+        self.arena.clear()
+        steps = int(min(max_steps, 2**31 - 1))
+        while True:
+            eng.teacher_rollout(self.kind, self.seed, steps, self.arena, num_tasks_scale=self.scales[0],
+                                work_scale=self.scales[1])
+            self.launches += 1
+            cur = self.arena.cursor.cpu().numpy()
+            if not (cur[:, _abi.CUR_FULL] != 0).any():
+                break
+            self.arena.grow(cur)
+            self.growths += 1
+        self._check_not_frozen()
+        wall = torch.as_tensor(self._host("wall_time"), dtype=torch.float64).to(self.arena.cursor.device).clone()
+        return self.arena.buffer(wall)

@@ -402,6 +402,28 @@ int ssim_decima_rollout_timed(ssim_handle* h, const float* params, int32_t num_p
                               int64_t workspace_bytes, const ssim_decima_samples* samples,
                               const ssim_decima_timed* timed, int32_t* action_log, void* stream);
 
+/* Teacher rollout: a device heuristic (`kind`: any SSIM_POLICY_* of ssim_rollout, the weighted-fair kinds included;
+ * `seed` keys the random kind's counter-based stream) drives every env in ONE persistent launch until its episode ends
+ * (terminated, or at the time limit of its reset), and every decision is left in `samples` (required) in the form the
+ * persistent Decima rollout records: the Decima features of the observation (ssim_decima_features) as node / edge /
+ * DAG rows and one ssim_decima_sample, same layout, cursor, full mark with cursor[5..7], wall_before and reward. The
+ * action fields: stage_idx the heuristic's index among the schedulable stages, num_exec the value handed to the step,
+ * job_idx the active-job (DAG) index of the chosen stage's node row, exec_idx = num_exec - 1, lgprob = 0. A NO-OP
+ * decision (the heuristic returns stage_idx = -1) is recorded too, as stage_idx = -1, job_idx = -1, exec_idx = 0 and
+ * the num_exec passed to the step, so the trajectory stays complete; a learner masks those samples out. Actions, final
+ * state and obs arena equal those of ssim_rollout(kind, seed) from the same reset. Collection mode only: `flags` must
+ * be 0 (SSIM_ROLLOUT_AUTORESET / PREEMPT / WARMUP / GREEDY: SSIM_E_ARG); an unknown kind, max_stages > 32 (the
+ * edge-mask word, as ssim_decima_features) and SJF-CP's own stage cap are SSIM_E_ARG. `workspace`: device memory of
+ * ssim_decima_workspace_bytes(h). action_log: optional device int32 [max_steps][num_envs][2], as ssim_rollout's. The
+ * kernel unit is ssim_debug_kernel_name(h, SSIM_DEBUG_TEACHER): "tr_lds" / "tr_hbm". */
+int ssim_teacher_rollout(ssim_handle* h, int32_t kind, uint64_t seed, float num_tasks_scale, float work_scale,
+                         int32_t max_steps, int32_t flags, void* workspace, int64_t workspace_bytes,
+                         const ssim_decima_samples* samples, int32_t* action_log, void* stream);
+/* Test hook (host only, no launch): a teacher-rollout decision keeps the features' scratch in the wave's LDS when its
+ * observation has at most *cap nodes and *dags DAGs (the rule and the plan of ssim_decima_rollout's one-wave units),
+ * else in the global workspace, so a test can say which placement a recorded decision took. */
+int ssim_debug_teacher_plan(const ssim_handle* h, int32_t* cap, int32_t* dags);
+
 const char* ssim_last_error(void);
 
 /* Test hook, not part of the drop-in surface: a trace of CPython-set operations (add / remove / idle order) on one
@@ -423,6 +445,7 @@ int ssim_debug_set_trace(ssim_handle* h, const int32_t* ops, int32_t n_ops, int3
 #define SSIM_DEBUG_PRIO 3 /* ssim_debug_kernel_name only: the unit an SJF / SJF-CP rollout on this handle launches */
 #define SSIM_DEBUG_DECIMA_GREEDY 4 /* ssim_debug_kernel_name only: the unit of a SSIM_ROLLOUT_GREEDY launch ("drg_*") */
 #define SSIM_DEBUG_WFAIR 5 /* ssim_debug_kernel_name only: the unit a weighted-fair rollout on this handle launches */
+#define SSIM_DEBUG_TEACHER 6 /* ssim_debug_kernel_name only: the unit ssim_teacher_rollout launches ("tr_lds" / "tr_hbm") */
 int ssim_debug_set_trace_ex(ssim_handle* h, const int32_t* ops, int32_t n_ops, int32_t width, int32_t* orders,
                             int32_t variant, void* stream);
 /* Name of the kernel translation unit a variant selects for this handle ("hbm_n100", "bench900", "dr_hbm50", ...; ""

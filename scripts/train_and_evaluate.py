@@ -11,7 +11,7 @@ next to nothing; the reference trains for 500 iterations on the TPC-H traces).
 
 Prints one table (mean and median over the envs of the episode's average job duration, in seconds) and one JSON line.
 
-    python scripts/train_and_evaluate.py [--iterations 3] [--envs 1024] [--model decima.pt]
+    python scripts/train_and_evaluate.py [--iterations 3] [--envs 1024] [--model decima.pt] [--init clone.pt]
 """
 
 from __future__ import annotations
@@ -36,6 +36,9 @@ def main() -> None:
     ap.add_argument("--seed", type=int, default=10000)
     ap.add_argument("--model", default=None, help="checkpoint path (default: a temporary file)")
     ap.add_argument("--steps-per-launch", type=int, default=1024)
+    ap.add_argument("--init", default=None, metavar="PATH",
+                    help="start PPO from this DecimaScheduler.save checkpoint (agent_cfg['init_checkpoint']), e.g. a "
+                         "behaviour-cloned policy of scripts/imitate_and_evaluate.py")
     args = ap.parse_args()
 
     import numpy as np
@@ -51,6 +54,8 @@ def main() -> None:
     dev = torch.device("cuda:0")
     cfg = {k: dict(v) for k, v in DECIMA_TPCH.items()}
     dataset = resolve_dataset(cfg["env"])
+    if args.init:
+        cfg["agent"]["init_checkpoint"] = args.init
     t0 = time.perf_counter()
     ppo = PPO(cfg["agent"], cfg["env"], cfg["trainer"], dataset=dataset, device=dev)
     hist = ppo.train(args.iterations, log=None)
