@@ -22,6 +22,7 @@
 #include "kernels.h"
 #include "decima.h"
 #include "decima_policy.h"
+#include "sample_arena.h"
 
 // 1: the HBM-resident Decima rollout keeps the executor records in LDS for the launch (Sim ex_lds), after which the
 // policy plan starts (sparksched.hip decima_lds_plan); 0 (default): in HBM, and the plan takes the wave's whole LDS share
@@ -37,6 +38,11 @@ struct DecimaWork {
   int64_t feat_scratch, plan, stride;  // per-env block
   int64_t feats, ccap, emask, depth;  // absolute offsets of the [num_envs] feature arrays
   int64_t packed, total;              // the packed policy weights (kDpPackedBytes), then the end
+  // the feature arrays in the workspace at `work`
+  __host__ __device__ DecimaFeatArrays arrays(uint8_t* work) const {
+    return {reinterpret_cast<float*>(work + feats), reinterpret_cast<int32_t*>(work + ccap),
+            reinterpret_cast<uint32_t*>(work + emask), reinterpret_cast<int32_t*>(work + depth)};
+  }
 };
 inline DecimaWork decima_work(const ssim_layout& L) {
   DecimaWork w{};
@@ -172,7 +178,7 @@ struct DecimaPolicy {
       const int64_t slot = (int64_t)eid * t.cap_resets + W::uni(sc[0]);
       const uint64_t seed = W::uni(t.seeds[slot]);
       const double limit = W::uni(t.limits[slot]);
-      const int last = W::uni(a.smp.cursor[(int64_t)eid * 8]) - 1;
+      const int last = W::uni(arena_cursor(a.smp, eid)[kCurSamples]) - 1;
       const int J = s.JC;
       for (int j = W::lane(); j < J; j += W::kWidth) {
         t.ep_arrival[slot * J + j] = s.jtimes(j).tarr;
@@ -200,22 +206,7 @@ struct DecimaPolicy {
       return false;
     const ssim_decima_samples& sm = a.smp;
     if (sm.rec == nullptr) return true;
-    const int32_t* cnt = reinterpret_cast<const int32_t*>(obs + P->L.ob_counts) + (int64_t)s.eid * SSIM_NUM_COUNTS;
-    int32_t* cur = sm.cursor + (int64_t)s.eid * 8;
-    if (W::uni(cur[0]) + 1 > sm.cap_samples || W::uni(cur[1]) + W::uni(cnt[SSIM_OC_NUM_NODES]) > sm.cap_nodes ||
-        W::uni(cur[2]) + W::uni(cnt[SSIM_OC_NUM_EDGES]) > sm.cap_edges ||
-        W::uni(cur[3]) + W::uni(cnt[SSIM_OC_NUM_JOBS]) > sm.cap_dags) {
-      W::sync();
-      if (W::lane() == 0) {  // region full: the host grows the arena (to fit what is recorded here), launches again
-        cur[4] = 1;
-        cur[5] = W::uni(cnt[SSIM_OC_NUM_NODES]);
-        cur[6] = W::uni(cnt[SSIM_OC_NUM_EDGES]);
-        cur[7] = W::uni(cnt[SSIM_OC_NUM_JOBS]);
-      }
-      W::sync();
-      return false;
-    }
-    return true;
+    return arena_has_room<W>(sm, P->L, obs, s.eid);
   }
   template <class S>
   __device__ __forceinline__ bool act(S& s, int k, StepIn* out) const {
@@ -224,28 +215,15 @@ struct DecimaPolicy {
     const int eid = s.eid;
     // (rollout_body calls can_act() first: an arena-full or finished env never gets here)
     const ssim_decima_samples& sm = a.smp;
-    const int32_t* cnt = reinterpret_cast<const int32_t*>(obs + L.ob_counts) + (int64_t)eid * SSIM_NUM_COUNTS;
-    const int n = W::uni(cnt[SSIM_OC_NUM_NODES]), ne = W::uni(cnt[SSIM_OC_NUM_EDGES]);
-    const int nj = W::uni(cnt[SSIM_OC_NUM_JOBS]);
-    int32_t* cur = sm.cursor + (int64_t)eid * 8;
-    int cs = 0, cn = 0, ce = 0, cg = 0;
-    if (sm.rec != nullptr) {
-      cs = W::uni(cur[0]);
-      cn = W::uni(cur[1]);
-      ce = W::uni(cur[2]);
-      cg = W::uni(cur[3]);
-    }
+    const ArenaSlot at = arena_slot<W>(sm, L, obs, eid, sm.rec != nullptr);
 #ifdef SSIM_PROFILE
     uint64_t tp = W::clock();
 #endif
     SSIM_MARK("decima_act_begin");
     uint8_t* wk = a.work + (int64_t)eid * a.wl.stride;
-    float* feats = reinterpret_cast<float*>(a.work + a.wl.feats);
-    int32_t* ccap = reinterpret_cast<int32_t*>(a.work + a.wl.ccap);
-    uint32_t* emask = reinterpret_cast<uint32_t*>(a.work + a.wl.emask);
-    int32_t* depth = reinterpret_cast<int32_t*>(a.work + a.wl.depth);
+    const DecimaFeatArrays fa = a.wl.arrays(a.work);
     // (timed: the lockstep async collector's stream, counter + the env's decision index in the call)
-    const uint64_t ctr = kTimed ? a.counter + (uint64_t)cs
+    const uint64_t ctr = kTimed ? a.counter + (uint64_t)at.cs
                                 : a.counter + (uint64_t)s.h.decisions + (a.autoreset ? (uint64_t)s.h.episode << 32 : 0ull);
     double before = 0.0;  // (timed) the sample's time: the call's elapsed time before the decision
     if constexpr (kTimed) {
@@ -260,10 +238,10 @@ struct DecimaPolicy {
 #else
     uint64_t* pprof = nullptr;
 #endif
-    const bool lds_plan = n <= a.plan_cap && nj <= kDpLdsDags;
+    const bool lds_plan = at.n <= a.plan_cap && at.nj <= kDpLdsDags;
     SSIM_MARK("decima_policy_begin");
-    const DpAction act = decima_decide<kHelp, kGreedy>(P, obs, a.weights, wk + a.wl.feat_scratch, wk + a.wl.plan, feats, ccap, emask,
-                                       depth, a.num_tasks_scale, a.work_scale, a.seed, ctr, eid,
+    const DpAction act = decima_decide<kHelp, kGreedy>(P, obs, a.weights, wk + a.wl.feat_scratch, wk + a.wl.plan, fa.feats, fa.ccap, fa.emask,
+                                       fa.depth, a.num_tasks_scale, a.work_scale, a.seed, ctr, eid,
                                        lds_plan ? a.plan_cap : 0,
                                        (uint32_t)(s.scr + a.plan_off - g_smem), pprof, (uint32_t)a.help_off);
     SSIM_MARK("decima_policy_end");
@@ -274,57 +252,9 @@ struct DecimaPolicy {
     out->stage_idx = act.stage_idx;
     out->num_exec = act.num_exec;
     if (a.test_reject && k == 0) out->num_exec = L.num_executors + 1;  // (test hook: an action the env refuses)
-    if (sm.rec != nullptr) {  // the observation as the learner's DagBatch rows (schedulers/decima.py build_batch)
-      const float* f = feats + (int64_t)eid * L.stage_cap * kDecimaFeatures;
-      const float* nodes = reinterpret_cast<const float*>(obs + L.ob_nodes) + (int64_t)eid * L.stage_cap * 3;
-      const int64_t* links = reinterpret_cast<const int64_t*>(obs + L.ob_edge_links) + (int64_t)eid * L.edge_cap * 2;
-      const int32_t* ptr = reinterpret_cast<const int32_t*>(obs + L.ob_dag_ptr) + (int64_t)eid * (L.job_cap + 1);
-      const int32_t* cc = ccap + (int64_t)eid * L.job_cap;
-      const uint32_t* em = emask + (int64_t)eid * L.edge_cap;
-      float* xn = sm.nodes + ((int64_t)eid * sm.cap_nodes + cn) * 6;
-      for (int i = W::lane(); i < n; i += W::kWidth) {
-#pragma unroll
-        for (int c = 0; c < kDecimaFeatures; ++c) xn[(int64_t)i * 6 + c] = f[(int64_t)i * kDecimaFeatures + c];
-        xn[(int64_t)i * 6 + 5] = nodes[3 * i + 2];
-      }
-      int32_t* ed = sm.edges + ((int64_t)eid * sm.cap_edges + ce) * 4;
-      for (int e = W::lane(); e < ne; e += W::kWidth) {
-        ed[4 * e + 0] = (int32_t)links[2 * e];
-        ed[4 * e + 1] = (int32_t)links[2 * e + 1];
-        ed[4 * e + 2] = (int32_t)em[e];
-        ed[4 * e + 3] = 0;
-      }
-      int32_t* dg = sm.dags + ((int64_t)eid * sm.cap_dags + cg) * 2;
-      for (int k = W::lane(); k < nj; k += W::kWidth) {
-        dg[2 * k + 0] = ptr[k + 1] - ptr[k];
-        dg[2 * k + 1] = cc[k];
-      }
-      const int dep = W::uni(depth[eid]);
-      W::sync();
-      if (W::lane() == 0) {
-        ssim_decima_sample r;
-        r.num_nodes = n;
-        r.num_edges = ne;
-        r.num_dags = nj;
-        r.depth = dep;
-        r.node_off = cn;
-        r.edge_off = ce;
-        r.dag_off = cg;
-        r.stage_idx = act.stage_idx;
-        r.job_idx = act.job_idx;
-        r.exec_idx = act.exec_idx;
-        r.num_exec = act.num_exec;
-        r.lgprob = act.lgprob;
-        r.wall_before = kTimed ? before : s.h.wall;
-        r.reward = 0.0;
-        sm.rec[(int64_t)eid * sm.cap_samples + cs] = r;
-        cur[0] = cs + 1;
-        cur[1] = cn + n;
-        cur[2] = ce + ne;
-        cur[3] = cg + nj;
-      }
-      W::sync();
-    }
+    if (sm.rec != nullptr)
+      arena_push<W>(sm, L, obs, eid, fa, at, {act.stage_idx, act.job_idx, act.exec_idx, act.num_exec, act.lgprob},
+                    kTimed ? before : s.h.wall);
 #ifdef SSIM_PROFILE
     s.prof_add(kPhDecRecord, W::clock() - tp);
 #endif
@@ -345,12 +275,7 @@ struct DecimaPolicy {
       W::sync();
     }
     if (sm.rec == nullptr) return;
-    const int eid = s.eid;
-    const int cs = W::uni(sm.cursor[(int64_t)eid * 8]);
-    const double r = W::uni(reinterpret_cast<const double*>(obs + P->L.ob_reward)[eid]);
-    W::sync();
-    if (W::lane() == 0 && cs > 0) sm.rec[(int64_t)eid * sm.cap_samples + cs - 1].reward = r;
-    W::sync();
+    arena_reward<W>(sm, P->L, obs, s.eid);
   }
   // The env refused the action act() recorded (it is frozen with SSIM_ERR_INVARIANT, the collector raises): the
   // sample and its observation rows come off the arena, so no sample ever holds an action the env did not take.
@@ -359,19 +284,7 @@ struct DecimaPolicy {
     using W = WaveHip;
     const ssim_decima_samples& sm = a.smp;
     if (sm.rec == nullptr) return;
-    W::sync();
-    if (W::lane() == 0) {
-      int32_t* cur = sm.cursor + (int64_t)s.eid * 8;
-      const int cs = cur[0];
-      if (cs > 0) {
-        const ssim_decima_sample& r = sm.rec[(int64_t)s.eid * sm.cap_samples + cs - 1];
-        cur[1] -= r.num_nodes;
-        cur[2] -= r.num_edges;
-        cur[3] -= r.num_dags;
-        cur[0] = cs - 1;
-      }
-    }
-    W::sync();
+    arena_take_back<W>(sm, s.eid);
   }
 };
 

@@ -759,6 +759,26 @@ extern "C" int64_t ssim_decima_workspace_bytes(const ssim_handle* h) {
   return decima_work(h->params.L).total;
 }
 
+// Argument checks the Decima and teacher rollout entries share (`who` names the entry in messages).
+static int check_sample_arena(const char* who, const ssim_decima_samples& sm) {
+  if (sm.cursor == nullptr || sm.rec == nullptr || sm.nodes == nullptr || sm.edges == nullptr || sm.dags == nullptr ||
+      sm.cap_samples <= 0 || sm.cap_nodes < 0 || sm.cap_edges < 0 || sm.cap_dags < 0)
+    return set_err(SSIM_E_ARG, "%s: incomplete sample arena", who);
+  return SSIM_OK;
+}
+static int check_decima_workspace(const char* who, const DecimaWork& wl, int64_t workspace_bytes) {
+  if (workspace_bytes < wl.total)
+    return set_err(SSIM_E_ARG, "%s: workspace of %lld B, needs %lld (ssim_decima_workspace_bytes)", who,
+                   (long long)workspace_bytes, (long long)wl.total);
+  return SSIM_OK;
+}
+static int check_edge_mask_depth(const char* who, const ssim_handle* h) {
+  if (h->params.C.max_stages > kDecimaMaxDepth)
+    return set_err(SSIM_E_ARG, "%s: max_stages %d > %d (edge-mask word)", who, h->params.C.max_stages,
+                   kDecimaMaxDepth);
+  return SSIM_OK;
+}
+
 // The checks and launch arguments ssim_decima_rollout and ssim_decima_rollout_timed share (`who` names the entry in
 // messages): the policy weights packed on `stream`, the workspace layout, the sample arena.
 static int decima_rollout_args(const char* who, ssim_handle* h, const float* params, int32_t num_params,
@@ -769,9 +789,7 @@ static int decima_rollout_args(const char* who, ssim_handle* h, const float* par
     return set_err(SSIM_E_ARG, "%s: %d parameters, the fused kernel implements the "
                    "decima_tpch.yaml architecture (%d)", who, num_params, kDecimaParams);
   const ssim_layout& L = h->params.L;
-  if (h->params.C.max_stages > kDecimaMaxDepth)
-    return set_err(SSIM_E_ARG, "%s: max_stages %d > %d (edge-mask word)", who, h->params.C.max_stages,
-                   kDecimaMaxDepth);
+  if (const int rc = check_edge_mask_depth(who, h); rc != SSIM_OK) return rc;
   if (L.num_executors > 64 * kDpExecChunks)
     return set_err(SSIM_E_ARG, "%s: more than %d executors", who, 64 * kDpExecChunks);
   // (the global plan's agg rows, stage_cap x 16 floats, hold the N exec scores too: decima_lds_plan)
@@ -779,16 +797,11 @@ static int decima_rollout_args(const char* who, ssim_handle* h, const float* par
     return set_err(SSIM_E_ARG, "%s: stage cap %d below ceil(%d executors / %d): the policy plan "
                    "cannot hold the exec scores", who, L.stage_cap, L.num_executors, kDpEmb);
   const DecimaWork wl = decima_work(L);
-  if (workspace_bytes < wl.total)
-    return set_err(SSIM_E_ARG, "%s: workspace of %lld B, needs %lld (ssim_decima_workspace_bytes)", who,
-                   (long long)workspace_bytes, (long long)wl.total);
+  if (const int rc = check_decima_workspace(who, wl, workspace_bytes); rc != SSIM_OK) return rc;
   DecimaRolloutArgs a{};
   if (samples != nullptr) {
-    const ssim_decima_samples& sm = *samples;
-    if (sm.cursor == nullptr || sm.rec == nullptr || sm.nodes == nullptr || sm.edges == nullptr || sm.dags == nullptr ||
-        sm.cap_samples <= 0 || sm.cap_nodes < 0 || sm.cap_edges < 0 || sm.cap_dags < 0)
-      return set_err(SSIM_E_ARG, "%s: incomplete sample arena", who);
-    a.smp = sm;
+    if (const int rc = check_sample_arena(who, *samples); rc != SSIM_OK) return rc;
+    a.smp = *samples;
   }
   a.weights = reinterpret_cast<const dp_f32x4*>(static_cast<uint8_t*>(workspace) + wl.packed);
   a.work = static_cast<uint8_t*>(workspace);
@@ -920,28 +933,18 @@ extern "C" int ssim_teacher_rollout(ssim_handle* h, int32_t kind, uint64_t seed,
   if (flags != 0)
     return set_err(SSIM_E_ARG, "ssim_teacher_rollout: collection mode only, flags must be 0 (no SSIM_ROLLOUT_AUTORESET / "
                    "PREEMPT / WARMUP / GREEDY; flags 0x%x)", flags);
-  if (h->params.C.max_stages > kDecimaMaxDepth)
-    return set_err(SSIM_E_ARG, "ssim_teacher_rollout: max_stages %d > %d (edge-mask word)", h->params.C.max_stages,
-                   kDecimaMaxDepth);
+  if (const int rc = check_edge_mask_depth("ssim_teacher_rollout", h); rc != SSIM_OK) return rc;
   if (samples == nullptr) return set_err(SSIM_E_ARG, "ssim_teacher_rollout: needs a sample arena");
-  const ssim_decima_samples& sm = *samples;
-  if (sm.cursor == nullptr || sm.rec == nullptr || sm.nodes == nullptr || sm.edges == nullptr || sm.dags == nullptr ||
-      sm.cap_samples <= 0 || sm.cap_nodes < 0 || sm.cap_edges < 0 || sm.cap_dags < 0)
-    return set_err(SSIM_E_ARG, "ssim_teacher_rollout: incomplete sample arena");
+  if (const int rc = check_sample_arena("ssim_teacher_rollout", *samples); rc != SSIM_OK) return rc;
   const ssim_layout& L = h->params.L;
   const DecimaWork wl = decima_work(L);
-  if (workspace_bytes < wl.total)
-    return set_err(SSIM_E_ARG, "ssim_teacher_rollout: workspace of %lld B, needs %lld (ssim_decima_workspace_bytes)",
-                   (long long)workspace_bytes, (long long)wl.total);
+  if (const int rc = check_decima_workspace("ssim_teacher_rollout", wl, workspace_bytes); rc != SSIM_OK) return rc;
   uint8_t* const work = static_cast<uint8_t*>(workspace);
   const DecimaLdsPlan pl = teacher_lds_plan(h->params);
   TeacherArgs a{};
   a.work = work + wl.feat_scratch;
   a.stride = wl.stride;
-  a.feats = reinterpret_cast<float*>(work + wl.feats);
-  a.ccap = reinterpret_cast<int32_t*>(work + wl.ccap);
-  a.emask = reinterpret_cast<uint32_t*>(work + wl.emask);
-  a.depth = reinterpret_cast<int32_t*>(work + wl.depth);
+  static_cast<DecimaFeatArrays&>(a) = wl.arrays(work);
   a.num_tasks_scale = num_tasks_scale;
   a.work_scale = work_scale;
   a.kind = kind;
@@ -949,7 +952,7 @@ extern "C" int ssim_teacher_rollout(ssim_handle* h, int32_t kind, uint64_t seed,
   a.plan_cap = pl.cap;
   a.plan_off = pl.off;
   a.plan_dags = kDpLdsDags;
-  a.smp = sm;
+  a.smp = *samples;
   const TeacherRolloutFn fn = pick_teacher(h->params);
   const int rc = lds_opt_in((const void*)fn, pl.lds);
   if (rc != SSIM_OK) return rc;

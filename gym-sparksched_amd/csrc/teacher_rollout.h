@@ -17,8 +17,7 @@
 // wants) IS recorded, as stage_idx = -1, job_idx = -1, exec_idx = 0 and the num_exec passed to the step, so the
 // trajectory, its times and rewards stay complete; the behaviour-cloning trainer masks those samples out.
 //
-// The record-writing code is a second copy of DecimaPolicy::act's, not a shared function: the k_dr_* / k_drt_* /
-// k_drg_* units then compile from exactly the code they had.
+// The arena is written through sample_arena.h, as DecimaPolicy writes it.
 //
 // The driver is independent of the wave type (the test-only host build runs it on the one-lane wave,
 // tests/hostsim/teacher.cpp); the kernels at the end are device-only.
@@ -30,16 +29,13 @@
 #include "policy.h"
 #include "rollout.h"
 #include "decima.h"
+#include "sample_arena.h"
 
 namespace ssim {
 
-struct TeacherArgs {
+struct TeacherArgs : DecimaFeatArrays {  // (the [num_envs] feature arrays, in the workspace)
   uint8_t* work;    // the global workspace: env e's feature scratch at work + e * stride (decima_rollout.h decima_work)
   int64_t stride;
-  float* feats;     // the [num_envs] feature arrays (the ssim_decima_features layout), in the workspace
-  int32_t* ccap;
-  uint32_t* emask;
-  int32_t* depth;
   float num_tasks_scale, work_scale;
   int32_t kind;     // SSIM_POLICY_*
   uint64_t seed;    // (the random kind's counter-based stream)
@@ -87,29 +83,12 @@ struct TeacherPolicy {
   TeacherArgs a;
 
   // Collection mode only: not when the episode is over (terminated, past its time limit, frozen, never reset), and not
-  // when the sample arena cannot hold the current observation (the full mark and the needs, as DecimaPolicy::can_act:
-  // the host grows the arena and launches again).
+  // when the sample arena cannot hold the current observation (the host grows the arena and launches again).
   template <class S>
   __device__ __forceinline__ bool can_act(const S& s) const {
     using W = typename S::WT;
     if (s.h.terminated || s.frozen() || s.h.wall >= s.h.time_limit || s.h.num_jobs == 0) return false;
-    const ssim_decima_samples& sm = a.smp;
-    const int32_t* cnt = reinterpret_cast<const int32_t*>(obs + P->L.ob_counts) + (int64_t)s.eid * SSIM_NUM_COUNTS;
-    int32_t* cur = sm.cursor + (int64_t)s.eid * 8;
-    if (W::uni(cur[0]) + 1 > sm.cap_samples || W::uni(cur[1]) + W::uni(cnt[SSIM_OC_NUM_NODES]) > sm.cap_nodes ||
-        W::uni(cur[2]) + W::uni(cnt[SSIM_OC_NUM_EDGES]) > sm.cap_edges ||
-        W::uni(cur[3]) + W::uni(cnt[SSIM_OC_NUM_JOBS]) > sm.cap_dags) {
-      W::sync();
-      if (W::lane() == 0) {
-        cur[4] = 1;
-        cur[5] = W::uni(cnt[SSIM_OC_NUM_NODES]);
-        cur[6] = W::uni(cnt[SSIM_OC_NUM_EDGES]);
-        cur[7] = W::uni(cnt[SSIM_OC_NUM_JOBS]);
-      }
-      W::sync();
-      return false;
-    }
-    return true;
+    return arena_has_room<W>(a.smp, P->L, obs, s.eid);
   }
 
   template <class S>
@@ -117,108 +96,38 @@ struct TeacherPolicy {
     using W = typename S::WT;
     const ssim_layout& L = P->L;
     const int eid = s.eid;
-    const ssim_decima_samples& sm = a.smp;
-    const int32_t* cnt = reinterpret_cast<const int32_t*>(obs + L.ob_counts) + (int64_t)eid * SSIM_NUM_COUNTS;
-    const int n = W::uni(cnt[SSIM_OC_NUM_NODES]), ne = W::uni(cnt[SSIM_OC_NUM_EDGES]);
-    const int nj = W::uni(cnt[SSIM_OC_NUM_JOBS]);
-    int32_t* cur = sm.cursor + (int64_t)eid * 8;
-    const int cs = W::uni(cur[0]), cn = W::uni(cur[1]), ce = W::uni(cur[2]), cg = W::uni(cur[3]);
+    const ArenaSlot at = arena_slot<W>(a.smp, L, obs, eid);
     // 1. the Decima features of the observation
-    if (n <= a.plan_cap && nj <= a.plan_dags)
+    if (at.n <= a.plan_cap && at.nj <= a.plan_dags)
       DecimaView<W>{L, obs, eid}.template run<false>(a.num_tasks_scale, a.work_scale, teacher_lds(s, a.plan_off),
                                                      a.feats, a.ccap, a.emask, a.depth, a.plan_cap);
     else
-      DecimaView<W>{L, obs, eid}.template run<true>(a.num_tasks_scale, a.work_scale,
-                                                    a.work + (int64_t)eid * a.stride, a.feats, a.ccap, a.emask, a.depth);
+      DecimaView<W>{L, obs, eid}.template run<true>(a.num_tasks_scale, a.work_scale, a.work + (int64_t)eid * a.stride,
+                                                    a.feats, a.ccap, a.emask, a.depth);
     // 2. the heuristic's action
     const StepIn act = sim_policy(s, a.kind, a.seed);
     *out = act;
-    // 3. the observation as the learner's DagBatch rows, and the record
-    const float* f = a.feats + (int64_t)eid * L.stage_cap * kDecimaFeatures;
+    // 3. the sample: the action in Decima's action space (a no-op as stage_idx = job_idx = -1, exec_idx = 0)
     const float* nodes = reinterpret_cast<const float*>(obs + L.ob_nodes) + (int64_t)eid * L.stage_cap * 3;
-    const int64_t* links = reinterpret_cast<const int64_t*>(obs + L.ob_edge_links) + (int64_t)eid * L.edge_cap * 2;
     const int32_t* ptr = reinterpret_cast<const int32_t*>(obs + L.ob_dag_ptr) + (int64_t)eid * (L.job_cap + 1);
-    const int32_t* cc = a.ccap + (int64_t)eid * L.job_cap;
-    const uint32_t* em = a.emask + (int64_t)eid * L.edge_cap;
     const int stage = W::uni(act.stage_idx), nexec = W::uni(act.num_exec);
-    const int job = stage >= 0 ? teacher_job_of<W>(nodes, ptr, n, nj, stage) : -1;
-    float* xn = sm.nodes + ((int64_t)eid * sm.cap_nodes + cn) * 6;
-    for (int i = W::lane(); i < n; i += W::kWidth) {
-      for (int c = 0; c < kDecimaFeatures; ++c) xn[(int64_t)i * 6 + c] = f[(int64_t)i * kDecimaFeatures + c];
-      xn[(int64_t)i * 6 + 5] = nodes[3 * i + 2];
-    }
-    int32_t* ed = sm.edges + ((int64_t)eid * sm.cap_edges + ce) * 4;
-    for (int e = W::lane(); e < ne; e += W::kWidth) {
-      ed[4 * e + 0] = (int32_t)links[2 * e];
-      ed[4 * e + 1] = (int32_t)links[2 * e + 1];
-      ed[4 * e + 2] = (int32_t)em[e];
-      ed[4 * e + 3] = 0;
-    }
-    int32_t* dg = sm.dags + ((int64_t)eid * sm.cap_dags + cg) * 2;
-    for (int k = W::lane(); k < nj; k += W::kWidth) {
-      dg[2 * k + 0] = ptr[k + 1] - ptr[k];
-      dg[2 * k + 1] = cc[k];
-    }
-    const int dep = W::uni(a.depth[eid]);
-    W::sync();
-    if (W::lane() == 0) {
-      ssim_decima_sample r;
-      r.num_nodes = n;
-      r.num_edges = ne;
-      r.num_dags = nj;
-      r.depth = dep;
-      r.node_off = cn;
-      r.edge_off = ce;
-      r.dag_off = cg;
-      r.stage_idx = stage >= 0 ? stage : -1;
-      r.job_idx = stage >= 0 ? job : -1;
-      r.exec_idx = stage >= 0 ? nexec - 1 : 0;
-      r.num_exec = nexec;
-      r.lgprob = 0.0f;
-      r.wall_before = s.h.wall;
-      r.reward = 0.0;
-      sm.rec[(int64_t)eid * sm.cap_samples + cs] = r;
-      cur[0] = cs + 1;
-      cur[1] = cn + n;
-      cur[2] = ce + ne;
-      cur[3] = cg + nj;
-    }
-    W::sync();
+    const int job = stage >= 0 ? teacher_job_of<W>(nodes, ptr, at.n, at.nj, stage) : -1;
+    arena_push<W>(a.smp, L, obs, eid, a, at,
+                  {stage >= 0 ? stage : -1, stage >= 0 ? job : -1, stage >= 0 ? nexec - 1 : 0, nexec, 0.0f}, s.h.wall);
     return true;
   }
 
   // the decision's reward (observe() wrote it to the obs arena) into its sample
   template <class S>
   __device__ __forceinline__ void done(S& s) const {
-    using W = typename S::WT;
-    const ssim_decima_samples& sm = a.smp;
-    const int eid = s.eid;
-    const int cs = W::uni(sm.cursor[(int64_t)eid * 8]);
-    const double r = W::uni(reinterpret_cast<const double*>(obs + P->L.ob_reward)[eid]);
-    W::sync();
-    if (W::lane() == 0 && cs > 0) sm.rec[(int64_t)eid * sm.cap_samples + cs - 1].reward = r;
-    W::sync();
+    arena_reward<typename S::WT>(a.smp, P->L, obs, s.eid);
   }
 
   // The env refused the recorded action (it is frozen with SSIM_ERR_INVARIANT): the sample and its rows come off the
-  // arena, as DecimaPolicy::rejected.
+  // arena.
   template <class S>
   __device__ __forceinline__ void rejected(S& s) const {
-    using W = typename S::WT;
-    const ssim_decima_samples& sm = a.smp;
-    W::sync();
-    if (W::lane() == 0) {
-      int32_t* cur = sm.cursor + (int64_t)s.eid * 8;
-      const int cs = cur[0];
-      if (cs > 0) {
-        const ssim_decima_sample& r = sm.rec[(int64_t)s.eid * sm.cap_samples + cs - 1];
-        cur[1] -= r.num_nodes;
-        cur[2] -= r.num_edges;
-        cur[3] -= r.num_dags;
-        cur[0] = cs - 1;
-      }
-    }
-    W::sync();
+    arena_take_back<typename S::WT>(a.smp, s.eid);
   }
 };
 

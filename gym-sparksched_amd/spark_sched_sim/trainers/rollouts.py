@@ -18,6 +18,16 @@ from ..wrappers import StochasticTimeLimitSampler
 from ..schedulers.decima import live_sizes, DagBatch, build_batch, cat_batches, select_envs
 
 
+def _check_not_frozen(counts, what: str) -> None:
+    """After a persistent rollout (`what` names it): no env of the obs arena's `counts` may be frozen."""
+    counts = counts.cpu().numpy() if isinstance(counts, torch.Tensor) else np.asarray(counts)
+    err = counts[:, _abi.OC_ERR] & _abi.SSIM_ERR_STICKY
+    if err.any():  # e.g. an action the engine refused (frozen with SSIM_ERR_INVARIANT): its samples are invalid
+        bad = np.flatnonzero(err)
+        raise RuntimeError(f"{what}: envs {bad[:8].tolist()} frozen with error bits "
+                           f"{[hex(int(x)) for x in err[bad[:8]]]}")
+
+
 class GpuRolloutBuffer:
     """Per decision step t: the live envs' observations as one DagBatch (select_envs order = `envs[t]`),
     actions, log-probs, rewards and the wall time before the step. `trajectories()` pads per-env rows."""
@@ -115,13 +125,6 @@ class RolloutCollector:
         # the kernel hashes (local env * C + counter); adding row_offset * C to the counter makes that the
         # hash of the global row (C: the constant below, csrc/decima_policy.h decima_policy_env)
         return (base + self.row_offset * 0x9E3779B97F4A7C15) & (2**64 - 1)
-
-    def _check_not_frozen(self) -> None:
-        err = self.engine.views["counts"][:, _abi.OC_ERR].cpu().numpy() & _abi.SSIM_ERR_STICKY
-        if err.any():  # e.g. an action the engine refused (frozen with SSIM_ERR_INVARIANT): its samples are invalid
-            bad = np.flatnonzero(err)
-            raise RuntimeError(f"decima rollout: envs {bad[:8].tolist()} frozen with error bits "
-                               f"{[hex(int(x)) for x in err[bad[:8]]]}")
 
     def _views(self, features: bool = True):
         eng = self.engine
@@ -273,6 +276,24 @@ class DecimaSampleArena:
                 setattr(self, names[i], self._grown(getattr(self, names[i]), cap))
         self.cursor[:, _abi.CUR_FULL:] = 0  # the flags and the recorded needs
 
+    def launch_until_fits(self, launch, again=None):
+        """Calls `launch()` (a persistent rollout into this arena) until it leaves no env with the full flag, growing
+        the arena after each launch that does; the envs continue where they stopped. `again(full)` (optional, called
+        after every launch): a reason of the caller's own to launch once more. Returns the last launch's cursor and
+        the numbers of launches and growths."""
+        launches = growths = 0
+        while True:
+            launch()
+            launches += 1
+            cur = self.cursor.cpu().numpy()
+            full = bool((cur[:, _abi.CUR_FULL] != 0).any())
+            if full:
+                self.grow(cur)
+                growths += 1
+            more = again is not None and again(full)
+            if not (full or more):
+                return cur, launches, growths
+
     def buffer(self, final_wall: torch.Tensor) -> "ArenaRolloutBuffer":
         return ArenaRolloutBuffer(self, final_wall)
 
@@ -389,15 +410,11 @@ class DeviceRolloutCollector(RolloutCollector):
         ctr = self._stream_counter((self.calls << 32) + 1)
         self.arena.clear()
         steps = int(min(max_steps, 2**31 - 1))
-        while True:
-            eng.decima_rollout(params, self.seed, ctr, steps, samples=self.arena, num_tasks_scale=self.scales[0],
-                               work_scale=self.scales[1])
-            self.launches += 1
-            cur = self.arena.cursor.cpu().numpy()
-            if not (cur[:, _abi.CUR_FULL] != 0).any():
-                break
-            self.arena.grow(cur)
-        self._check_not_frozen()
+        _, launches, _ = self.arena.launch_until_fits(
+            lambda: eng.decima_rollout(params, self.seed, ctr, steps, samples=self.arena,
+                                       num_tasks_scale=self.scales[0], work_scale=self.scales[1]))
+        self.launches += launches
+        _check_not_frozen(eng.views["counts"], "decima rollout")
         wall = eng.views["wall_time"].double().clone()
         return self.arena.buffer(wall)
 
@@ -594,27 +611,24 @@ class DeviceAsyncRolloutCollector(AsyncRolloutCollector):
                 self.ep_completed, self.ep_state)
         steps = int(min(max_steps, 2**31 - 1))
         resets: list = []
-        while True:
-            eng.decima_rollout_timed(params, self.seed, ctr, steps, self.arena, timed, tensors=keep,
-                                     num_tasks_scale=self.scales[0], work_scale=self.scales[1])
-            self.launches += 1
-            cur = self.arena.cursor.cpu().numpy()
+
+        def again(full: bool) -> bool:  # the slots the launch consumed; once more if a row used up its schedule
+            nonlocal seeds, limits
             sc = self.sched.cpu().numpy()
-            used = sc[:, _abi.SCHED_USED]
+            used, out = sc[:, _abi.SCHED_USED], bool((sc[:, _abi.SCHED_EXHAUSTED] != 0).any())
             if used.any():
                 self._consume(used, seeds, limits, resets)
-            full = (cur[:, _abi.CUR_FULL] != 0).any()
-            out = (sc[:, _abi.SCHED_EXHAUSTED] != 0).any()
-            if not (full or out):
-                break
-            if full:
-                self.arena.grow(cur)
-                self.growths += 1
-            if out:
-                self.refills += 1
-            if used.any():  # the next launch's slots continue each row's seed stream
-                seeds, limits = self._fill_schedule()
-        self._check_not_frozen()
+                if full or out:  # the next launch's slots continue each row's seed stream
+                    seeds, limits = self._fill_schedule()
+            self.refills += out
+            return out
+
+        _, launches, growths = self.arena.launch_until_fits(
+            lambda: eng.decima_rollout_timed(params, self.seed, ctr, steps, self.arena, timed, tensors=keep,
+                                             num_tasks_scale=self.scales[0], work_scale=self.scales[1]), again)
+        self.launches += launches
+        self.growths += growths
+        _check_not_frozen(eng.views["counts"], "decima rollout")
         self.next_wall = eng.views["wall_time"].double().clone()
         buf = self.arena.buffer(self.clock[:, 0].clone())  # times are elapsed times: the final one closes each row
         buf.resets = sorted(resets, key=lambda r: (r[1], r[0]))  # (env, step) in the lockstep loop's order
@@ -662,13 +676,6 @@ class TeacherRolloutCollector:
         v = self.engine.views[name] if self.on_device else self.engine.host_views()[name]
         return v.cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
 
-    def _check_not_frozen(self) -> None:
-        err = self._host("counts")[:, _abi.OC_ERR] & _abi.SSIM_ERR_STICKY
-        if err.any():
-            bad = np.flatnonzero(err)
-            raise RuntimeError(f"teacher rollout: envs {bad[:8].tolist()} frozen with error bits "
-                               f"{[hex(int(x)) for x in err[bad[:8]]]}")
-
     @torch.no_grad()
     def collect(self, seeds, time_limits=None, max_steps: int = 10**9) -> ArenaRolloutBuffer:
         self.calls += 1
@@ -677,15 +684,11 @@ class TeacherRolloutCollector:
         eng.reset_sampled(_abi.SSIM_RESET_SEED, seeds=seeds, time_limits=limits)
         self.arena.clear()
         steps = int(min(max_steps, 2**31 - 1))
-        while True:
-            eng.teacher_rollout(self.kind, self.seed, steps, self.arena, num_tasks_scale=self.scales[0],
-                                work_scale=self.scales[1])
-            self.launches += 1
-            cur = self.arena.cursor.cpu().numpy()
-            if not (cur[:, _abi.CUR_FULL] != 0).any():
-                break
-            self.arena.grow(cur)
-            self.growths += 1
-        self._check_not_frozen()
+        _, launches, growths = self.arena.launch_until_fits(
+            lambda: eng.teacher_rollout(self.kind, self.seed, steps, self.arena, num_tasks_scale=self.scales[0],
+                                        work_scale=self.scales[1]))
+        self.launches += launches
+        self.growths += growths
+        _check_not_frozen(self._host("counts"), "teacher rollout")
         wall = torch.as_tensor(self._host("wall_time"), dtype=torch.float64).to(self.arena.cursor.device).clone()
         return self.arena.buffer(wall)

@@ -536,28 +536,31 @@ def gpu_collect(eng, params, arena, seed: int, counter: int, max_steps=None, bud
     or pending; with `max_steps`, ONE launch of at most that many decisions per env, the arena left as it is. No env
     may end with error bits. Returns launches, grown (arena growths) and full (the last launch filled the arena)."""
     launches = grown = 0
-    prev = -1
-    while True:
-        if budget:
+    full = False
+    if max_steps is not None:
+        eng.decima_rollout(params, seed, counter, max_steps, flags=flags, samples=arena)
+        launches = 1
+        full = bool((arena.cursor[:, _abi.CUR_FULL] != 0).any())
+    elif not budget:  # (the collectors' loop)
+        _, launches, grown = arena.launch_until_fits(
+            lambda: eng.decima_rollout(params, seed, counter, 10**6, flags=flags, samples=arena))
+    else:
+        prev = -1
+        while True:
             eng.decima_rollout(params, seed, counter, 64, budget, flags=flags | _abi.SSIM_ROLLOUT_PREEMPT,
                                samples=arena)
-        else:
-            eng.decima_rollout(params, seed, counter, 10**6 if max_steps is None else max_steps, flags=flags,
-                               samples=arena)
-        launches += 1
-        cur = arena.cursor.cpu().numpy()
-        full = bool((cur[:, _abi.CUR_FULL] != 0).any())
-        if max_steps is not None:
-            break
-        if full:
-            arena.grow(cur)
-            grown += 1
-            continue
-        n = int(cur[:, _abi.CUR_SAMPLES].sum())
-        pend = int(np.count_nonzero(eng.views["counts"][:, _abi.OC_ERR].cpu().numpy() & _abi.SSIM_ERR_PENDING))
-        if not budget or (n == prev and pend == 0):
-            break
-        prev = n
+            launches += 1
+            cur = arena.cursor.cpu().numpy()
+            full = bool((cur[:, _abi.CUR_FULL] != 0).any())
+            if full:
+                arena.grow(cur)
+                grown += 1
+                continue
+            n = int(cur[:, _abi.CUR_SAMPLES].sum())
+            pend = int(np.count_nonzero(eng.views["counts"][:, _abi.OC_ERR].cpu().numpy() & _abi.SSIM_ERR_PENDING))
+            if n == prev and pend == 0:
+                break
+            prev = n
     torch.cuda.synchronize()
     err = eng.views["counts"][:, _abi.OC_ERR].cpu().numpy()
     assert not err.any(), [hex(int(x)) for x in err]

@@ -47,7 +47,7 @@ struct HostTeacherPolicy : TeacherPolicy {
   template <class S>
   void done(S& s) const {
     TeacherPolicy::done(s);
-    const int cs = a.smp.cursor[(int64_t)s.eid * 8];
+    const int cs = arena_cursor(a.smp, s.eid)[kCurSamples];
     if (cs <= 0) return;
     ssim_decima_sample& r = a.smp.rec[(int64_t)s.eid * a.smp.cap_samples + cs - 1];
     r.reward = wave_order_reward(s, r.wall_before, r.reward);
@@ -100,6 +100,29 @@ int hs_teacher_rollout(hs_handle* h, int kind, uint64_t seed, float nts, float w
   }
   free(lds);
   return 0;
+}
+
+// One call of sample_arena.h on the one-lane wave, no engine: env `eid` of a hand-made observation arena `obs` (byte
+// offsets ob = {counts, nodes, edge_links, dag_ptr, reward}, row caps = {stage, edge, job}) and feature arrays `fa`.
+// op 0: arena_has_room (returned), 1: arena_push of `act` = {stage_idx, job_idx, exec_idx, num_exec}, lgprob and
+// wall_before at the cursor, 2: arena_reward, 3: arena_take_back.
+int hs_arena_op(int op, const ssim_decima_samples* sm, int eid, const uint8_t* obs, const int64_t* ob,
+                const int32_t* caps, float* feats, int32_t* ccap, uint32_t* emask, int32_t* depth, const int32_t* act,
+                float lgprob, double wall_before) {
+  using W = WaveSerial;
+  ssim_layout L{};
+  L.ob_counts = ob[0], L.ob_nodes = ob[1], L.ob_edge_links = ob[2], L.ob_dag_ptr = ob[3], L.ob_reward = ob[4];
+  L.stage_cap = caps[0], L.edge_cap = caps[1], L.job_cap = caps[2];
+  switch (op) {
+    case 0: return arena_has_room<W>(*sm, L, obs, eid);
+    case 1:
+      arena_push<W>(*sm, L, obs, eid, {feats, ccap, emask, depth}, arena_slot<W>(*sm, L, obs, eid),
+                    {act[0], act[1], act[2], act[3], lgprob}, wall_before);
+      return 0;
+    case 2: arena_reward<W>(*sm, L, obs, eid); return 0;
+    case 3: arena_take_back<W>(*sm, eid); return 0;
+  }
+  return -1;
 }
 
 }  // extern "C"

@@ -15,7 +15,8 @@ from .driver import HERE, REPO, HostEngine
 
 SO_PATH = os.path.join(HERE, "_hostsim_teacher.so")
 SOURCES = [os.path.join(HERE, "teacher.cpp"),
-           os.path.join(REPO, "gym-sparksched_amd", "csrc", "teacher_rollout.h")] + driver.SOURCES
+           os.path.join(REPO, "gym-sparksched_amd", "csrc", "teacher_rollout.h"),
+           os.path.join(REPO, "gym-sparksched_amd", "csrc", "sample_arena.h")] + driver.SOURCES
 
 _lib = None
 
@@ -49,6 +50,7 @@ def lib():
         vp, i64 = ct.c_void_p, ct.c_int64
         L.hs_teacher_rollout.argtypes = [vp, ct.c_int, ct.c_uint64, ct.c_float, ct.c_float, ct.c_int, vp, i64, i64,
                                          i64, i64, i64, ct.c_int, ct.c_int, vp, vp]
+        L.hs_arena_op.argtypes = [ct.c_int, vp, ct.c_int, vp, vp, vp, vp, vp, vp, vp, vp, ct.c_float, ct.c_double]
         _lib = L
     return _lib
 

@@ -268,3 +268,107 @@ def test_ppo_starts_from_the_saved_clone(dataset, tmp_path):
     hist = ppo.train(1, log=None)  # and it trains from there
     assert len(hist) == 1 and np.isfinite(hist[0]["policy loss"])
     assert not torch.equal(ppo.scheduler.packed_params("cpu"), bc.scheduler.packed_params("cpu"))
+
+
+def test_sample_arena_known_answers():
+    """csrc/sample_arena.h (the one writer behind the Decima and teacher rollouts) on the one-lane wave, no engine:
+    room check, push, reward write-back and take-back on env 1 of a hand-made two-env observation arena (3 nodes,
+    2 edges, 2 DAGs; row caps 4 / 3 / 3) and a sample arena of 2 samples / 6 node / 4 edge / 3 DAG rows per env."""
+    import ctypes as ct
+
+    from hostsim import teacher_driver
+    from spark_sched_sim.trainers.rollouts import DecimaSampleArena
+
+    B, S, E, J = 2, 4, 3, 3
+    counts = np.zeros((B, _abi.NUM_COUNTS), np.int32)
+    nodes, links = np.zeros((B, S, 3), np.float32), np.zeros((B, E, 2), np.int64)
+    dag_ptr, reward = np.zeros((B, J + 1), np.int32), np.zeros(B, np.float64)
+    feats, ccap = np.zeros((B, S, 5), np.float32), np.zeros((B, J), np.int32)
+    emask, depth = np.zeros((B, E), np.uint32), np.zeros(B, np.int32)
+    obs_parts = [counts, nodes, links, dag_ptr, reward]  # (every part a multiple of 8 bytes: the offsets stay aligned)
+    ob = np.cumsum([0] + [p.nbytes for p in obs_parts[:-1]]).astype(np.int64)
+    caps = np.array([S, E, J], np.int32)
+    arena = DecimaSampleArena(B, "cpu", cap_samples=2, cap_nodes=6, cap_edges=4, cap_dags=3)
+    ptr = lambda a: a.ctypes.data  # noqa: E731
+
+    def observe(base):  # env 1's observation, every value marked by `base`
+        counts[1, [_abi.OC_NUM_NODES, _abi.OC_NUM_EDGES, _abi.OC_NUM_JOBS]] = 3, 2, 2
+        nodes[1, :3] = [[base + 1, base + 2, 1.0], [base + 3, base + 4, 0.0], [base + 5, base + 6, 1.0]]
+        links[1, :2] = [[0, 1], [2, 0]] if base else [[0, 1], [1, 2]]
+        dag_ptr[1, :3] = [0, 2, 3] if base else [0, 1, 3]
+        feats[1, :3] = base + 10.0 * np.arange(3)[:, None] + np.arange(5)[None, :]
+        ccap[1, :2] = [base + 4, base + 7]
+        emask[1, :2] = [base + 1, base + 2]
+        depth[1] = 2 + (base != 0)
+
+    def op(code, eid=1, act=(0, 0, 0, 0), lgprob=0.0, wall=0.0):
+        obs = np.frombuffer(b"".join(p.tobytes() for p in obs_parts), np.uint8)
+        st, a = arena.struct(), np.array(act, np.int32)
+        return teacher_driver.lib().hs_arena_op(code, ct.byref(st), eid, ptr(obs), ptr(ob), ptr(caps), ptr(feats),
+                                                ptr(ccap), ptr(emask), ptr(depth), ptr(a), lgprob, wall)
+
+    def cursor(e=1):
+        return arena.cursor[e].tolist()
+
+    def record(k, e=1):
+        r = arena.rec[e, k]
+        f = {name: int(r[i]) for i, name in enumerate(_abi.SAMPLE_I32)}
+        f64 = r.view(torch.float64)
+        return f, float(r[_abi.SAMPLE_LGPROB:_abi.SAMPLE_LGPROB + 1].view(torch.float32)), \
+            float(f64[_abi.SAMPLE_WALL]), float(f64[_abi.SAMPLE_REWARD])
+
+    def rows_of(base, links_, sizes):  # the node, edge and DAG rows arena_push writes for observe(base)
+        x = np.concatenate([base + 10.0 * np.arange(3)[:, None] + np.arange(5)[None, :], [[1.0], [0.0], [1.0]]], axis=1)
+        ed = [[links_[0][0], links_[0][1], base + 1, 0], [links_[1][0], links_[1][1], base + 2, 0]]
+        return x.astype(np.float32), np.array(ed, np.int32), np.array([[sizes[0], base + 4], [sizes[1], base + 7]], np.int32)
+
+    def check_rows(at, want):
+        cn, ce, cg = at
+        assert np.array_equal(arena.nodes[1, cn:cn + 3].numpy(), want[0])  # the 5 feature columns, the flag column
+        assert np.array_equal(arena.edges[1, ce:ce + 2].numpy(), want[1])  # links, the edge mask word, 0
+        assert np.array_equal(arena.dags[1, cg:cg + 2].numpy(), want[2])   # DAG sizes, executor caps
+
+    # 1. the first push
+    observe(0)
+    assert op(0) == 1 and cursor() == [0] * 8
+    op(1, act=(1, 0, 2, 3), lgprob=-0.5, wall=10.0)
+    assert cursor() == [1, 3, 2, 2, 0, 0, 0, 0]
+    first = ({"num_nodes": 3, "num_edges": 2, "num_dags": 2, "depth": 2, "node_off": 0, "edge_off": 0, "dag_off": 0,
+              "stage_idx": 1, "job_idx": 0, "exec_idx": 2, "num_exec": 3}, -0.5, 10.0, 0.0)
+    got = record(0)
+    assert {k: got[0][k] for k in first[0]} == first[0] and got[1:] == first[1:]
+    rows0 = rows_of(0, [[0, 1], [1, 2]], [1, 2])
+    check_rows((0, 0, 0), rows0)
+    # 2. the second observation does not fit (2 + 2 DAG rows > 3): the full mark and the needs, nothing else moves
+    observe(100)
+    assert op(0) == 0
+    assert cursor() == [1, 3, 2, 2, 1, 3, 2, 2]
+    assert DecimaSampleArena.required(arena.cursor.numpy()) == [2, 6, 4, 4]
+    # 3. the DAG region grown to exactly what is needed: the push fills every region to its cap
+    arena.dags, arena.caps[3] = DecimaSampleArena._grown(arena.dags, 4), 4
+    arena.cursor[:, _abi.CUR_FULL:] = 0
+    assert op(0) == 1 and cursor() == [1, 3, 2, 2, 0, 0, 0, 0]
+    op(1, act=(-1, -1, 0, 5), lgprob=0.0, wall=20.0)
+    assert cursor() == [2, 6, 4, 4, 0, 0, 0, 0]
+    got = record(1)
+    assert (got[0]["node_off"], got[0]["edge_off"], got[0]["dag_off"], got[0]["depth"]) == (3, 2, 2, 3)
+    assert (got[0]["stage_idx"], got[0]["job_idx"], got[0]["exec_idx"], got[0]["num_exec"]) == (-1, -1, 0, 5)
+    assert got[1:] == (0.0, 20.0, 0.0)
+    check_rows((3, 2, 2), rows_of(100, [[0, 1], [2, 0]], [2, 1]))
+    check_rows((0, 0, 0), rows0)
+    assert op(0) == 0 and cursor() == [2, 6, 4, 4, 1, 3, 2, 2]  # (no third sample)
+    arena.cursor[:, _abi.CUR_FULL:] = 0
+    # 4. the reward lands in the last record only
+    reward[1] = -7.25
+    op(2)
+    assert record(1)[3] == -7.25 and record(0)[3] == 0.0
+    # 5. the take-back restores the cursor after the first push; record 0 and its rows stay
+    op(3)
+    assert cursor() == [1, 3, 2, 2, 0, 0, 0, 0]
+    got = record(0)
+    assert {k: got[0][k] for k in first[0]} == first[0] and got[1:] == first[1:]
+    check_rows((0, 0, 0), rows0)
+    # 6. a take-back on an empty cursor is a no-op; env 0 was never written
+    op(3, eid=0)
+    assert cursor(0) == [0] * 8
+    assert not arena.rec[0].any() and not arena.nodes[0].any() and not arena.edges[0].any() and not arena.dags[0].any()
